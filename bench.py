@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the SpMM measurement of BASELINE.json, one JSON line per run.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|2|3|4|5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|2|3|4|5] [--full] [--dump-outputs DIR]
 
 One "step" = one full SpMM C = A @ B through the C ABI of libmispmm.so with A, B and C resident in HBM.
 
@@ -11,18 +11,25 @@ One "step" = one full SpMM C = A @ B through the C ABI of libmispmm.so with A, B
            4         large_20000 (ACTIVSg10K) BSR block 16 x K=128 bf16 (MFMA)
            5         large_25605 CSR x K=512 fp32  (row-sharded when --gpus N > 1)
 
-N = 1.  W eager warm-up steps, then the K timed steps are captured once into a hipGraph on the bench stream.
-A step lasts a few microseconds, so a single replay of a small K would time the launch latency of the graph and
-the clock ramp instead of the kernel: the graph is therefore replayed untimed for >= 50 ms (precondition) and
-then R times back to back inside one HIP-event pair, R chosen so that the timed region lasts >= 20 ms; that is
-repeated for 5 rounds.  A graph of fewer than 1000 launches holds the K steps several times over (two consecutive
-hipGraphLaunch calls leave the GPU idle for ~7 us: graph-API machinery, reported as `graph_of_exactly_steps_us`).  `ms_per_step`, `value` and `roofline` come from the MEDIAN round's event time divided by
-K * R launches; min and the spread are reported beside it; `replays` = R.  K and W are used exactly as passed.
-Where the gathered operand B sits in memory moves the time of one binary on one box by up to 6 % (profiles/r3/
-placement_probe.log: fresh copies of B and C in one process), so the whole measurement above is made on `--placements`
-(default 5) freshly allocated copies of B and C and the line reports the MEDIAN copy; `timing.placements_us` lists them all.
+N = 1.  W eager warm-up steps, then the K timed steps are captured into hipGraphs of at most 1000 launches on the bench
+stream.  The first graph is replayed untimed for >= 50 ms (precondition: clocks and caches in steady state), and the last
+of those replays is still running when one HIP-event pair around the K timed steps is queued behind it, so the host
+latency of the first launch stays out of the timed region.  `ms_per_step` = that event time / K, and `value` and
+`roofline` follow from it: K and W are used exactly as passed and K steps are timed, no more.  Two consecutive
+hipGraphLaunch calls leave the GPU idle for ~7 us (graph-API machinery), once per 1000 steps here: a K of a few dozen
+carries that gap over few steps, a K of thousands does not.  --dump-outputs DIR writes C of the last timed step.
 
-`hbm_streaming` (N = 1, every configuration): the steady-state loop above multiplies the same B into the same C, so its
+A plain run does only that.  `--full` measures and checks everything beside it, after the headline:
+  * the replayed steady state: the K steps captured into graphs of >= 1000 launches (a shorter graph holds them several
+    times over; `graph_of_exactly_steps_us` is the graph of exactly K), replayed R times back to back inside one HIP-event
+    pair, R chosen so that the timed region lasts >= 20 ms, 5 rounds, median round.  Where the gathered operand B sits in
+    memory moves the time of one binary on one box by up to 6 % (profiles/r3/placement_probe.log: fresh copies of B and C
+    in one process), so that is done on `--placements` (default 5) freshly allocated copies of B and C; `timing` lists
+    them all (`placements_us`) and reports the MEDIAN copy;
+  * `hbm_streaming`, `other_acc_mode`, `batched`, `other_bsr_kernels`, the live `roofline.traffic` and `cpu_baseline`
+    (below).
+
+`hbm_streaming` (N = 1, --full, every configuration): the steady-state loop above multiplies the same B into the same C, so its
 working set (17-66 MB) never leaves the 256 MiB Infinity Cache -- `value` is that figure, as BASELINE.json defines the metric.
 Beside it the SAME kernel is timed over S distinct (B, C) pairs in rotation, S = ceil(512 MiB / (bytes of B + C)) (headline:
 32 pairs, 522 MB), captured into one hipGraph whose launch count is a multiple of S, so that every launch reads a B and
@@ -30,7 +37,7 @@ writes a C that 2 x 256 MiB of other operands have passed the caches since: B st
 the same matrix every step) stays cached.  It is also the honest form of the reference's timing contract -- one cold,
 un-warmed launch per kernel (reference/src/engine/engine.cpp:41-44) -- without the event-pair overhead of a single shot.
 
-`roofline.traffic` is measured in the same run: before this process touches the GPU it runs the configuration twice as a
+`roofline.traffic` (--full) is measured in the same run: before this process touches the GPU it runs the configuration twice as a
 child under `rocprofv3 --pmc` (FETCH_SIZE, WRITE_SIZE: separate passes, eager launches); profiles/r3/traffic.json is the
 fallback (--no-extras / --no-live-traffic skip the passes).
 
@@ -41,9 +48,10 @@ nnz-balanced ranges, B is broadcast once (outside the timed region), every rank 
 and the C row slabs are exchanged in buckets: `allgather` (RCCL all_gather_into_tensor on a second stream) or
 `peer` (the kernel's slab is copied straight into every peer's C over xGMI through IPC-mapped buffers).  `value`
 is end to end (kernels + exchange, max over ranks); `kernel_only` re-runs the steps with C left row-sharded.
-Strong scaling: the total work is fixed as N grows.
+Strong scaling: the total work is fixed as N grows.  This line is unchanged by --full: its timed region is the K steps
+repeated R times (>= 20 ms), and it always carries its CPU leg; --dump-outputs writes rank 0's exchanged C.
 
-The CPU leg (`cpu_baseline`) is the oracle under oracle/ -- a port of the reference's sequential CPU engine --
+The CPU leg (`cpu_baseline`, --full at N = 1) is the oracle under oracle/ -- a port of the reference's sequential CPU engine --
 timed on this host with 1 thread, and also the checker of the GPU result that was just timed: a mismatch
 refuses to print a number.
 """
@@ -69,6 +77,7 @@ ROUNDS = 5
 WATCHDOG_EXIT = 3                # exit code of every rank when an exchange mode hung and the watchdog printed the partial line
 MIN_GRAPH_NODES = 1000           # launches per captured graph (the K steps are captured ceil(1000 / K) times over)
 STREAM_BYTES = 512 << 20        # (B, C) pairs in rotation for the HBM-streamed figure: twice the 256 MiB Infinity Cache
+DUMP_BYTES = 64 << 20           # --dump-outputs: at most this much in all
 TRAFFIC_JSON = os.path.join(ROOT, "profiles", "r4", "traffic.json")
 _REAL_STDOUT = None
 
@@ -100,6 +109,14 @@ def parse():
                    help="N>1: how C slabs travel: `allgather` (default) = RCCL all_gather_into_tensor, `peer` = direct stores into "
                         "IPC-mapped peer buffers (has only ever run between processes on one card), `both` measures the two and "
                         "reports the faster as `value`")
+    p.add_argument("--full", action="store_true",
+                   help="N=1: after the headline, also measure and check everything beside it (off by default): the replayed steps "
+                        "on --placements copies of B and C, the HBM-streamed loop, the other accumulate mode, the batched launch, "
+                        "the other BSR kernels, the live PMC traffic and the CPU baseline that checks the GPU result.  "
+                        "--no-extras, --no-cpu-baseline, --no-live-traffic, --hbm-streaming, --placements and --cpu-seconds choose among them")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write C of the last timed step as DIR/c.npy (float32; above 64 MB a fixed, seeded sample of its rows, their "
+                        "indices in DIR/c_rows.npy)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--mode-timeout", type=int, default=240,
                    help="N>1: seconds an exchange mode after the first measured one may take before the line is printed without it (0 = wait)")
@@ -121,7 +138,10 @@ def parse():
     p.add_argument("--placements", type=int, default=5,
                    help="N=1: time the K steps on this many freshly allocated copies of B and C and report the MEDIAN copy "
                         "(every copy is listed under timing.placements); 1 = the operands as first allocated")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ workloads
@@ -449,6 +469,42 @@ class Timer:
         self.capi.check(self.l.mispmm_event_elapsed_ms(self.ev0, self.ev1, ctypes.byref(ms)))
         return ms.value, wall * 1e3
 
+    def time_steps(self, fn, steps, use_graph=True, precondition_s=PRECONDITION_S):
+        """The headline measurement: exactly `steps` calls of fn inside one HIP-event pair (captured into hipGraphs of at
+        most 1000 launches unless eager).  Before it, >= precondition_s of untimed replays of the first graph (clocks and
+        caches in steady state, every graph uploaded); the last batch of them is still in flight when the event pair and the
+        timed launches are queued, so the host latency of the first timed launch is not in the timed region."""
+        import torch
+        chunk = min(steps, MIN_GRAPH_NODES)
+        graphs = self.capture(fn, steps) if use_graph else None
+        warm = graphs[:1] if use_graph else None
+        distinct = list({g.value: g for g in graphs}.values()) if use_graph else []
+        for g in distinct:                                 # graph upload / first touch, untimed
+            self.capi.check(self.l.mispmm_graph_launch(g, self.sp))
+        if not use_graph:
+            self._pass(None, fn, chunk)
+        ms1, _ = self.event_ms(lambda: self._pass(warm, fn, chunk))
+        per_sync = max(1, int(0.005 / max(ms1 * 1e-3, 1e-7)))
+        t_end = time.perf_counter() + precondition_s
+        n_pre = 0
+        while time.perf_counter() < t_end or n_pre < 2:
+            for _ in range(per_sync):
+                self._pass(warm, fn, chunk)
+            torch.cuda.synchronize()
+            n_pre += 1
+        for _ in range(per_sync):                          # in flight while the timed region is queued behind it
+            self._pass(warm, fn, chunk)
+        ms = ctypes.c_float()
+        self.capi.check(self.l.mispmm_event_record(self.ev0, self.sp))
+        self._pass(graphs, fn, steps)
+        self.capi.check(self.l.mispmm_event_record(self.ev1, self.sp))
+        torch.cuda.synchronize()
+        self.capi.check(self.l.mispmm_event_elapsed_ms(self.ev0, self.ev1, ctypes.byref(ms)))
+        for g in distinct:
+            self.capi.check(self.l.mispmm_graph_destroy(g))
+        return {"ms": ms.value, "us_per_step": ms.value * 1e3 / steps, "graph_nodes": chunk if use_graph else 0,
+                "graph_launches": len(graphs) if use_graph else 0}
+
     def measure(self, fn, steps, use_graph=True, timed_s=TIMED_S, precondition_s=PRECONDITION_S, rounds=ROUNDS,
                 min_nodes=MIN_GRAPH_NODES):
         """Per-step statistics of `steps` captured calls of fn, replayed R times per round (see module docstring).
@@ -587,9 +643,26 @@ def stream_loop(w, stream, nsets):
     return fn, nsets * max(1, -(-MIN_GRAPH_NODES // nsets)), nsets, pairs
 
 
+def dump_outputs(directory, arrays):
+    """--dump-outputs: what the timed path computed in its last step, as DIR/<name>.npy in float32, at most DUMP_BYTES in
+    all.  A larger output is cut to a fixed, seeded sample of its rows; their indices go beside it as <name>_rows.npy
+    (float64, exact)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            row_bytes = a.nbytes // max(1, a.shape[0]) + 8
+            keep = max(1, min(a.shape[0], int(DUMP_BYTES * (a.nbytes / total)) // row_bytes))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(directory, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
 def run_single(args):
     # children only: nothing in this process has touched the GPU yet
-    want_live = not (args.no_live_traffic or args.no_extras or args.launch != "graph")
+    want_live = args.full and not (args.no_live_traffic or args.no_extras or args.launch != "graph")
     live = live_traffic(args, args.operand_sets) if want_live else None
     live_stream = live_traffic(args, 0) if want_live and args.operand_sets == 1 and args.hbm_streaming != "off" else None
     import torch
@@ -609,27 +682,33 @@ def run_single(args):
     torch.cuda.synchronize()
     kernel_tag = capi.last_kernel()
 
-    stats = []
+    stats, head = [], None
     if rotating:
-        # --operand-sets: the main loop itself is the HBM-streamed form (profiler children, experiments)
+        # --operand-sets: the main loop itself is the HBM-streamed form (profiler children, experiments); timed as whole
+        # rotations replayed for >= 20 ms per round (module docstring), not as exactly K steps
         fn, launches, nsets, pairs = stream_loop(w, stream, args.operand_sets)
         stats.append(timer.measure(fn, launches, use_graph=args.launch == "graph", min_nodes=1))
+        launch_us = stats[0]["median_us"]
+        step()                            # leave the timed mode's result in C
+        torch.cuda.synchronize()
     else:
-        # The same K steps on `--placements` fresh copies of B and C: where the gathered operand sits in memory moves the time
-        # of one binary on one box by up to 6 % (profiles/r3/placement_probe.log), so a single allocation is a draw from that
-        # range; the line reports the MEDIAN copy and lists them all.
+        head = timer.time_steps(step, args.steps, use_graph=args.launch == "graph")
+        launch_us = head["us_per_step"]
+    got = w.host_result()                 # C of the last timed step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"c": got})
+    if args.full and not rotating:
+        # The same K steps on `--placements` fresh copies of B and C, each replayed for >= 20 ms per round: where the gathered
+        # operand sits in memory moves the time of one binary on one box by up to 6 % (profiles/r3/placement_probe.log), so a
+        # single allocation is a draw from that range; the line lists the median round of every copy.
         for i in range(max(1, args.placements)):
             if i:
                 w.fresh_operands()
                 step()
                 torch.cuda.synchronize()
             stats.append(timer.measure(step, args.steps, use_graph=args.launch == "graph"))
-    stat = sorted(stats, key=lambda s: s["median_us"])[(len(stats) - 1) // 2]
-    step()                                # leave the timed mode's result in C for the parity check
-    torch.cuda.synchronize()
-    got = w.host_result()
+    stat = sorted(stats, key=lambda s: s["median_us"])[(len(stats) - 1) // 2] if stats else None
 
-    launch_us = stat["median_us"]
     achieved = w.abytes / (launch_us * 1e-6) / 1e9
     traffic, traffic_src = load_traffic(f"{args.config}:{w.matrix}/{w.n}/{args.acc}" + ("/nohint" if os.environ.get("MISPMM_NO_HINT") == "1" else ""),
                                         kernel_tag)
@@ -648,21 +727,17 @@ def run_single(args):
         "config": {"workload": w.workload, "baseline_config": args.config, "kernel": args.kernel,
                    "kernel_tag": kernel_tag, "acc_mode": args.acc if w.has_fast else "fp32 accumulate (MFMA)",
                    "launch": args.launch, "device": info["name"], **w.extra_config},
-        "timing": {"method": f"the {args.steps} steps captured into hipGraphs of {stat['graph_nodes']} launches, the steps "
-                             f"replayed {stat['replays']}x per round inside one HIP-event pair, {stat['rounds']} rounds, after "
-                             f">= {int(PRECONDITION_S * 1e3)} ms of untimed replays; value / ms_per_step / roofline use the median round",
-                   "replays": stat["replays"], "rounds": stat["rounds"], "median_us": round(stat["median_us"], 4),
-                   "min_us": round(stat["min_us"], 4), "max_us": round(stat["max_us"], 4),
-                   "host_wall_us_per_step": round(stat["wall_us"], 4),
-                   "placements_us": [round(x["median_us"], 4) for x in stats],
-                   "placements_note": f"the timed steps were run on {len(stats)} freshly allocated copies of B and C (median round of each "
-                                      "listed in allocation order); value / ms_per_step / roofline are those of the MEDIAN copy: "
-                                      "operand placement alone moves these kernels by up to 6 %"},
+        "timing": ({"method": (f"the {args.steps} timed steps captured into hipGraphs of {head['graph_nodes']} launches "
+                               f"({head['graph_launches']} graph launch{'es' if head['graph_launches'] != 1 else ''})" if head["graph_nodes"] else f"the {args.steps} timed steps launched eagerly")
+                              + f" inside one HIP-event pair, queued behind >= {int(PRECONDITION_S * 1e3)} ms of untimed replays of the "
+                              f"same steps; ms_per_step = the event time / {args.steps}",
+                    "timed_steps": args.steps, "timed_ms": round(head["ms"], 4)} if head else
+                   {"method": f"{stat['replays']} launches of whole rotations over {nsets} (B, C) pairs per round inside one HIP-event "
+                              f"pair, {stat['rounds']} rounds; value / ms_per_step / roofline use the median round"}),
         "achieved_hbm_GBps": round(achieved, 1),
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                      "algorithmic_bytes_per_launch": w.abytes, "launch_us": round(launch_us, 4),
-                     "frac_at_min": round(w.abytes / (stat["min_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
                      "note": "launch_us = HIP-event time of the timed region / launches in it (inter-kernel gaps "
                              "included); traffic = L2<->fabric bytes per launch from rocprofv3 PMC: " + str(traffic_src),
                      "residency": "the steady-state loop multiplies the same A, B into the same C: the working set "
@@ -675,12 +750,25 @@ def run_single(args):
     }
     out["roofline"]["traffic_source"] = ("live" if live is not None and live[0] is not None and live[1] == kernel_tag
                                          else "committed fallback" if traffic is not None else None)
+    if args.full and not rotating:
+        out["timing"].update({
+            "replayed_method": f"the {args.steps} steps captured into hipGraphs of {stat['graph_nodes']} launches, the steps replayed "
+                               f"{stat['replays']}x per round inside one HIP-event pair, {stat['rounds']} rounds, after >= "
+                               f"{int(PRECONDITION_S * 1e3)} ms of untimed replays; median round of the median copy of B and C",
+            "replays": stat["replays"], "rounds": stat["rounds"], "median_us": round(stat["median_us"], 4),
+            "min_us": round(stat["min_us"], 4), "max_us": round(stat["max_us"], 4),
+            "host_wall_us_per_step": round(stat["wall_us"], 4),
+            "placements_us": [round(x["median_us"], 4) for x in stats],
+            "placements_note": f"the replayed steps were run on {len(stats)} freshly allocated copies of B and C (median round of each "
+                               "listed in allocation order); median_us / min_us / max_us are those of the MEDIAN copy: operand "
+                               "placement alone moves these kernels by up to 6 %"})
+        out["roofline"]["frac_at_min"] = round(w.abytes / (stat["min_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
     if rotating:
         out["config"]["operand_sets"] = nsets
         out["roofline"]["residency"] = (f"the timed loop rotates over {nsets} distinct (B, C) pairs ({nsets * w.pair_bytes() / 1e6:.0f} MB): "
                                         "B streams from HBM, C streams to it; only A stays cached")
         del pairs
-    elif args.hbm_streaming == "on" or (args.hbm_streaming == "auto" and not args.no_extras):
+    elif args.full and (args.hbm_streaming == "on" or (args.hbm_streaming == "auto" and not args.no_extras)):
         # The HBM-streamed figure (module docstring): the same kernel over S distinct (B, C) pairs in rotation, 2 x the Infinity
         # Cache of them, one graph of a whole number of rotations replayed back to back inside one HIP-event pair.
         fn, launches, nsets, pairs = stream_loop(w, stream, 0)
@@ -714,7 +802,7 @@ def run_single(args):
         out["roofline"]["bytes_note"] = ("algorithmic_bytes_per_launch = the operand of the kernel that ran (column lists + bf16 "
                                          "tiles of the occupied columns) + B (bf16) + C (fp32); bsr16_operand_bytes = the same "
                                          "with the dense 16 x 16 bf16 blocks of the BSR file as A (SURVEY 8(d) config 4)")
-    if not args.no_extras and w.fmt == "bsr":
+    if args.full and not args.no_extras and w.fmt == "bsr":
         out["other_bsr_kernels"] = {}
         for other in ("slots", "steps", "dense"):
             if other == w.which:
@@ -726,7 +814,7 @@ def run_single(args):
                 "roofline_frac": round(w.kernel_bytes[other] / (o["median_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
         w.step(stream)
         torch.cuda.synchronize()
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         if args.launch == "graph" and args.steps < MIN_GRAPH_NODES:
             g = timer.measure(step, args.steps, rounds=3, precondition_s=0.01, min_nodes=1)
             out["timing"]["graph_of_exactly_steps_us"] = round(g["median_us"], 4)
@@ -760,7 +848,7 @@ def run_single(args):
                                       "bytes per product against the 8 TB/s HBM peak (8 operands = the Infinity-Cache regime of DESIGN.md "
                                       "section 5.6, where a single launch takes longer than the L2-resident loop behind `value`)"}
             del bs, cs
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(w, args.cpu_seconds, got, args.acc)
     emit(out)
 
@@ -1092,7 +1180,10 @@ def run_multi(args):
         except Exception as e:  # noqa: BLE001  (an optional leg never costs the line)
             extras["kernel_only_batched"] = {"unavailable": f"{type(e).__name__}: {e}"}
     if rank == 0:
-        emit(compose())
+        line = compose()
+        if args.dump_outputs and gathered_host is not None:
+            dump_outputs(args.dump_outputs, {"c": gathered_host})
+        emit(line)
     dist.barrier()
     dist.destroy_process_group()
 

@@ -166,14 +166,14 @@ def test_cli_long_row_matrix_takes_the_split_kernel(tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg", ["headline", "2", "3", "4", "5"])
 def test_bench_line_contract(bench_line, cfg):
-    """bench.py at the driver's flags, every BASELINE configuration: the line carries the contract's fields, the GPU result
+    """bench.py --full (tests/conftest.py::bench_line), every BASELINE configuration: the line carries the contract's fields, the GPU result
     that was timed equals the oracle's (bench.py refuses to print otherwise), `roofline` and `hbm_streaming` follow from
     their own numbers.  No assertion on a time here (tests/test_zz_perf_gpu.py holds those)."""
     line = bench_line(cfg)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "hbm_streaming"):
         assert key in line, key
-    assert line["steps"] == 20 and line["warmup"] == 5 and line["n_gpus"] == 1 and line["vs_baseline"] is None
+    assert line["steps"] == 2000 and line["warmup"] == 5 and line["n_gpus"] == 1 and line["vs_baseline"] is None
     assert line["cpu_baseline"]["gpu_parity"] == ("bit-exact" if cfg != "4" else "within 2e-6 of sum|a||b| (bf16-rounded inputs, fp32 accumulate)")
     r = line["roofline"]
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and 0 < r["frac"] < 1

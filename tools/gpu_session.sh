@@ -10,8 +10,8 @@
 #   perf              pytest -m "gpu and perf"              (every assertion on a time; tests/test_zz_perf_gpu.py)
 #   tests             pytest -m gpu -x                      (what the driver runs: parity first, perf last)
 #   smoke             python __graft_entry__.py smoke
-#   bench             bench.py at the driver's flags        -> bench_default.json
-#   configs           bench.py --config 2 3 4 5             -> bench_cfg<N>.json
+#   bench             bench.py --full at --steps 20 --warmup 5 -> bench_default.json
+#   configs           bench.py --full --config 2 3 4 5      -> bench_cfg<N>.json
 #   general           the general CSR entry point (MISPMM_NO_HINT=1) -> bench_general_entry.json
 #   trace             rocprofv3 --kernel-trace --stats of the driver's command, digest of the timed kernel
 #   pmc               the PMC passes of every configuration + traffic.json (tools/profile_r4.sh)
@@ -40,12 +40,12 @@ for step in "$@"; do
     perf)   timeout -k 10 900 python3 -m pytest tests -m "gpu and perf" -q 2>&1 | tail -25 | tee "$OUT/pytest_perf.log" || exit 1;;
     tests)  timeout -k 10 1100 python3 -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee "$OUT/pytest_gpu.log" || exit 1;;
     smoke)  timeout -k 10 300 python3 __graft_entry__.py smoke 2>&1 | tail -3 | tee "$OUT/smoke.log" || exit 1;;
-    bench)  timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { tail -20 "$OUT/bench_default.err"; exit 1; }
+    bench)  timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { tail -20 "$OUT/bench_default.err"; exit 1; }
             show "$OUT/bench_default.json" headline;;
     configs) for c in 2 3 4 5; do
-              timeout -k 10 600 python3 bench.py --config $c --steps 20 --warmup 5 > "$OUT/bench_cfg$c.json" 2> "$OUT/bench_cfg$c.err" || { tail -20 "$OUT/bench_cfg$c.err"; exit 1; }
+              timeout -k 10 600 python3 bench.py --config $c --steps 20 --warmup 5 --full > "$OUT/bench_cfg$c.json" 2> "$OUT/bench_cfg$c.err" || { tail -20 "$OUT/bench_cfg$c.err"; exit 1; }
               show "$OUT/bench_cfg$c.json" "config $c"; done;;
-    general) MISPMM_NO_HINT=1 timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_general_entry.json" 2> "$OUT/bench_general.err" || exit 1
+    general) MISPMM_NO_HINT=1 timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > "$OUT/bench_general_entry.json" 2> "$OUT/bench_general.err" || exit 1
              show "$OUT/bench_general_entry.json" "general entry";;
     dist)   # the one-process-per-GPU driver on the one card: 1 rank over RCCL (torchrun form, as the driver launches it) and 2 ranks sharing the card
             MISPMM_FORCE_DIST=1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29577 \

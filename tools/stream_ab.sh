@@ -8,7 +8,7 @@ export MISPMM_LIB=cuda-optimization-for-spmm_amd/libmispmm_tune.so
 for spec in "k128:--config headline" "k256:--config headline --k-cols 256" "cfg3:--config 3" "cfg5:--config 5"; do
   tag=${spec%%:*}; args=${spec#*:}
   for s in 0 1; do
-    MISPMM_STREAM=$s timeout -k 10 300 python3 bench.py $args --steps 20 --warmup 5 --no-extras --hbm-streaming on --cpu-seconds 1 --no-live-traffic "$@" \
+    MISPMM_STREAM=$s timeout -k 10 300 python3 bench.py $args --steps 20 --warmup 5 --full --no-extras --hbm-streaming on --cpu-seconds 1 --no-live-traffic "$@" \
         > "$OUT/stream_ab_${tag}_$s.json" 2> "$OUT/stream_ab_${tag}_$s.err" || { tail -5 "$OUT/stream_ab_${tag}_$s.err"; exit 1; }
     python3 - "$OUT/stream_ab_${tag}_$s.json" "$tag stream=$s" <<'PY'
 import json, sys
