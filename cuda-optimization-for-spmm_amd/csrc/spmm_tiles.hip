@@ -14,7 +14,7 @@
 
 namespace mispmm {
 
-constexpr uint32_t kTileCols = 128;   // distinct columns per tile = the LDS budget (x 256 B = 32 KiB); a tile holds <= 16 rows (one per lane group)
+constexpr uint32_t kTileCols = MISPMM_LDS_TILE_COLS;   // distinct columns per tile = the LDS budget (x 256 B = 32 KiB); a tile holds <= 16 rows (one per lane group)
 
 // DMA: the slices go from the buffer load straight into LDS (buffer_load_dwordx4 ... lds: a wave's four lane groups stage four
 // CONSECUTIVE list positions = 1 KiB contiguous, exactly what one LDS-DMA instruction writes) instead of through registers and
@@ -134,7 +134,7 @@ static void launch_tiles(hipStream_t st, uint32_t numTiles, const uint32_t *tile
 
 using namespace mispmm;
 
-extern "C" int mispmm_csr_lds_tile_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t rowNnz, uint32_t numTiles,
+extern "C" int mispmm_csr_lds_tile_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t rowNnz, uint32_t numTiles, uint32_t maxTileCols,
                                        const uint32_t *tileRowPtrs, const uint32_t *tileColPtrs, const uint32_t *tileCols, const uint8_t *slots,
                                        const float *vals, const uint32_t *rowMap, const float *B, uint32_t N, uint32_t ldb, float *C,
                                        uint32_t ldc, int acc_mode) {
@@ -144,6 +144,9 @@ extern "C" int mispmm_csr_lds_tile_f32(mispmm_stream_t stream, uint32_t M, uint3
     if (!tileRowPtrs || !tileColPtrs || !tileCols || !slots || !vals || !rowMap) return fail(MISPMM_ERR_INVALID_ARG, "csr_lds_tile: null pointer");
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
     if (rowNnz == 0 || rowNnz > 16) return fail(MISPMM_ERR_UNSUPPORTED, "csr_lds_tile: rows of one width of 1..16 entries (got %u)", rowNnz);
+    // the kernel stages list positions 0 .. kTileCols - 1 only: a longer list would name slots past the LDS image
+    if (maxTileCols > kTileCols)
+        return fail(MISPMM_ERR_UNSUPPORTED, "csr_lds_tile: a tile lists %u columns, the LDS image holds %u", maxTileCols, kTileCols);
     const XcdTiling t = xcd_tiling(N, pick_vec(B, ldb, C, ldc, N), K);
     if (pick_vec(B, ldb, C, ldc, N) != 4 || N % t.q != 0 || (N / t.q) % 64 != 0 || static_cast<uint64_t>(K) * ldb * 4u > 0x7FFFFFFFull ||
         static_cast<uint64_t>(M) * ldc * 4u > 0x7FFFFFFFull || static_cast<uint64_t>(ceil_div(numTiles, 1u << t.log2p)) >= (1u << 24))

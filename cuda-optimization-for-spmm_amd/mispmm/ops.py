@@ -317,7 +317,9 @@ class DeviceCOO:
 
     @staticmethod
     def from_host(coo, device="cuda"):
-        order = np.lexsort((coo.col_idxs, coo.row_idxs))
+        """Entries sorted by row only, a row's entries in storage order: the reference (spmm_coo.cpp) adds them into the row
+        in that order, so sorting them by column as well would change the fp32 sums."""
+        order = np.argsort(np.asarray(coo.row_idxs), kind="stable")
         rows = np.asarray(coo.row_idxs)[order]
         row_ptrs = np.searchsorted(rows, np.arange(coo.num_rows + 1)).astype(np.uint32)
         return DeviceCOO(coo.num_rows, coo.num_cols, coo.nnz, _dev_u32(rows, device),
@@ -437,6 +439,7 @@ class DeviceCSRTiles:
     row_nnz: int
     num_tiles: int
     num_listed: int              # sum of the tiles' column lists = B-row slices staged per column part (nnz without sharing)
+    max_tile_cols: int           # the longest column list of a tile (the kernel declines lists longer than its LDS image)
     tile_row_ptrs: torch.Tensor
     tile_col_ptrs: torch.Tensor
     tile_cols: torch.Tensor
@@ -459,7 +462,8 @@ class DeviceCSRTiles:
         tc, order, slots = np.zeros(max(nl.value, 1), np.uint32), np.zeros(csr.num_rows, np.uint32), np.zeros(max(csr.nnz, 1), np.uint8)
         capi.check(l.mispmm_csr_tiles_host(*head, trp.ctypes.data, tcp.ctypes.data, tc.ctypes.data, order.ctypes.data, slots.ctypes.data))
         planned = permute_rows(csr, order)
-        return DeviceCSRTiles(csr.num_rows, csr.num_cols, csr.nnz, w, nt.value, nl.value, _dev_u32(trp, device), _dev_u32(tcp, device),
+        widest = int(np.diff(tcp.astype(np.int64)).max()) if nt.value else 0
+        return DeviceCSRTiles(csr.num_rows, csr.num_cols, csr.nnz, w, nt.value, nl.value, widest, _dev_u32(trp, device), _dev_u32(tcp, device),
                               _dev_u32(tc, device), torch.from_numpy(slots).to(device), _dev_f32(planned.data, device), _dev_u32(order, device))
 
 
@@ -470,9 +474,9 @@ def spmm_csr_tiles(a, b, out=None, acc="reference", stream=None):
         raise ValueError(f"B has {b.shape[0]} rows, A has {a.num_cols} columns")
     n = b.shape[1]
     c = _out(a.num_rows, n, b, out)
-    capi.check(capi.lib().mispmm_csr_lds_tile_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.row_nnz, a.num_tiles, _p(a.tile_row_ptrs),
-                                                  _p(a.tile_col_ptrs), _p(a.tile_cols), _p(a.slots), _p(a.data), _p(a.row_map), _p(b), n,
-                                                  _dense_ld(b), _p(c), _dense_ld(c), capi.ACC_MODES[acc]))
+    capi.check(capi.lib().mispmm_csr_lds_tile_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.row_nnz, a.num_tiles, a.max_tile_cols,
+                                                  _p(a.tile_row_ptrs), _p(a.tile_col_ptrs), _p(a.tile_cols), _p(a.slots), _p(a.data),
+                                                  _p(a.row_map), _p(b), n, _dense_ld(b), _p(c), _dense_ld(c), capi.ACC_MODES[acc]))
     return c
 
 

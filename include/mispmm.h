@@ -241,11 +241,15 @@ int mispmm_autotune_pick(const float *times_us, uint32_t n, float min_gain);
  *                           position i (= the kernel's rowMap; permute vals with mispmm_csr_permute_rows_host); slots[nnz]: per
  *                           entry, in plan order, the position of its column in its tile's list.
  *   mispmm_csr_lds_tile_f32 C = A * B from those arrays; REFERENCE mode bit-exact (a row keeps its entries in storage order).
- *                           MISPMM_ERR_UNSUPPORTED for other shapes (column parts that are not whole 64-column groups, ...). */
+ *                           maxTileCols: the longest column list of a tile (max of tileColPtrs[t + 1] - tileColPtrs[t]), which
+ *                           the caller knows from the host builder; the kernel stages at most MISPMM_LDS_TILE_COLS list
+ *                           positions, so tiles built with maxCols above that are MISPMM_ERR_UNSUPPORTED, as are other
+ *                           shapes (column parts that are not whole 64-column groups, ...). */
+#define MISPMM_LDS_TILE_COLS 128u
 int mispmm_csr_tiles_host(uint32_t M, uint32_t K, const uint32_t *rowPtrs_host, const uint32_t *colIdxs_host, uint32_t maxRows,
                           uint32_t maxCols, uint32_t *numTiles_out, uint32_t *numListed_out, uint32_t *tileRowPtrs_out_host,
                           uint32_t *tileColPtrs_out_host, uint32_t *tileCols_out_host, uint32_t *order_out_host, uint8_t *slots_out_host);
-int mispmm_csr_lds_tile_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t rowNnz, uint32_t numTiles,
+int mispmm_csr_lds_tile_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t rowNnz, uint32_t numTiles, uint32_t maxTileCols,
                             const uint32_t *tileRowPtrs, const uint32_t *tileColPtrs, const uint32_t *tileCols, const uint8_t *slots,
                             const float *vals, const uint32_t *rowMap, const float *B, uint32_t N, uint32_t ldb, float *C, uint32_t ldc,
                             int acc_mode);

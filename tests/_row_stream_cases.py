@@ -10,8 +10,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "cuda-optimization-for-spmm_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from mispmm import capi, formats, ops, synth  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
+
+import _adversarial as adv  # noqa: E402
+from _bits import assert_gap_untouched, assert_same_bits, sentinel_buffer  # noqa: E402
 
 
 def uniform_csr(m, k, w, seed):
@@ -77,6 +81,55 @@ def main():
         assert np.array_equal(got, ref), ("ell", m, k, w, n, capi.last_kernel())
         cases += 1
         print("ell", m, k, w, n, capi.last_kernel())
+    # the adversarial corpus (tests/_adversarial.py) on rows of one width: order discriminators, signed zeros, poisoned B rows,
+    # NaN gap columns of B and a sentinel in those of C, A arrays whose tails past nnz are NaN / name a poisoned row -- bit for bit
+    def nan_gap(b):
+        buf = torch.full((b.shape[0], b.shape[1] + 4), float("nan"), device="cuda")
+        buf[:, :b.shape[1]] = dev(b)
+        return buf[:, :b.shape[1]]
+
+    def tail(t, fill):
+        buf = torch.empty(t.numel() + 37, dtype=t.dtype, device=t.device)
+        buf[t.numel():] = fill
+        buf[:t.numel()].copy_(t)
+        return buf[:t.numel()]
+
+    zero = adv.poisoned_uniform(np.float32(np.nan), n=128, width=12)
+    zero.csr.data[:] = -np.abs(zero.csr.data)
+    zero.csr.data[::5] = -0.0
+    zero.b[:, 0::4], zero.b[:, 1::4] = 0.0, -0.0
+    zero.name = "signed_zero_uniform12"
+    adversarial = 0
+    for case in (adv.order_uniform(n=128, width=16), adv.order_uniform(n=128, width=11), zero,
+                 adv.poisoned_uniform(np.float32(np.nan), n=128, width=14), adv.poisoned_uniform(np.float32(np.inf), n=128, width=9)):
+        csr, b = case.csr, case.b
+        m, n = csr.num_rows, b.shape[1]
+        a = ops.DeviceCSR.from_host(csr, plan=False)
+        if case.poison is not None:
+            a.col_idxs, a.data = tail(a.col_idxs, int(case.poison_cols[0])), tail(a.data, float("nan"))
+        c = sentinel_buffer(m, n, n + 4, torch)
+        ops.spmm_csr(a, nan_gap(b), out=c[:, :n])
+        assert "row_stream" in capi.last_kernel(), (case.name, capi.last_kernel())
+        assert_same_bits(c[:, :n], orc.spmm_csr(csr.row_ptrs, csr.col_idxs, csr.data, b), f"row_stream csr {case.name}")
+        assert_gap_untouched(c, n, f"row_stream csr {case.name}")
+        # the same rows as a row-major ELL with padding slots in the middle and at the end of rows
+        ell = formats.csr_to_ell_rowmajor(csr)
+        pad = np.zeros(ell.col_idxs.shape, bool)
+        pad[:, 3] = pad[::3, -1] = True
+        cols, vals = ell.col_idxs.copy(), ell.data.copy()
+        cols[pad], vals[pad] = 0xFFFFFFFF, 0.0
+        keep = ~pad.reshape(-1)
+        rows = np.repeat(np.arange(m, dtype=np.uint32), ell.width)[keep]
+        want = orc.spmm_coo(m, rows, cols.reshape(-1)[keep], vals.reshape(-1)[keep], b)
+        c = sentinel_buffer(m, n, n + 4, torch)
+        ops.spmm_ell(ops.DeviceELL.from_host(formats.ELLRowMajor(m, csr.num_cols, int(keep.sum()), ell.width, cols, vals), compact=False),
+                     nan_gap(b), out=c[:, :n])
+        assert "row_stream" in capi.last_kernel(), (case.name, capi.last_kernel())
+        assert_same_bits(c[:, :n], want, f"row_stream ell {case.name}")
+        assert_gap_untouched(c, n, f"row_stream ell {case.name}")
+        adversarial += 1
+        print("adversarial", case.name, capi.last_kernel())
+    print(f"row_stream adversarial cases ok: {adversarial}")
     # shapes without an instance keep the row-gather kernel (width > 16, width < 9, N not a multiple of 32 per column part)
     for m, k, w, n in ((500, 300, 17, 128), (500, 300, 8, 128), (500, 300, 14, 40)):
         csr = uniform_csr(m, k, w, 5)

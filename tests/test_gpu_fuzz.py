@@ -9,6 +9,8 @@ import pytest
 torch = pytest.importorskip("torch")
 from mispmm import formats, ops  # noqa: E402
 
+from _bits import assert_same_bits  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 SCALE = int(os.environ.get("MISPMM_FUZZ_SCALE", "1"))   # more seeds for an occasional deep run
 
@@ -60,16 +62,16 @@ def test_fuzz_csr_coo_ell(oracle, seed):
     for kern in (0, 1, 2, 3, 4, 5):
         out = padded_out(m, n, rng)
         ops.spmm_csr(a, bd, out=out, kernel=kern)
-        assert np.array_equal(out.cpu().numpy(), ref), f"seed {seed} CSR kernel {kern} M={m} K={k} N={n}"
+        assert_same_bits(out, ref, f"seed {seed} CSR kernel {kern} M={m} K={k} N={n}")
     coo = formats.csr_to_coo(csr)
     ref32 = oracle.spmm_coo(m, coo.row_idxs, coo.col_idxs, coo.data, b)
     for ws in (True, False):
-        assert np.array_equal(ops.spmm_coo(ops.DeviceCOO.from_host(coo), bd, workspace=ws).cpu().numpy(), ref32)
+        assert_same_bits(ops.spmm_coo(ops.DeviceCOO.from_host(coo), bd, workspace=ws), ref32, f"seed {seed} COO workspace={ws}")
     ellc = formats.csr_to_ell_colmajor(csr)
-    assert np.array_equal(oracle.spmm_ell_colmajor(m, ellc.row_idxs, ellc.data, b), ref32)
+    assert_same_bits(oracle.spmm_ell_colmajor(m, ellc.row_idxs, ellc.data, b), ref32, f"seed {seed} ELL oracle")
     out = padded_out(m, n, rng)
     ops.spmm_ell(ops.DeviceELL.from_host(ellc), bd, out=out)
-    assert np.array_equal(out.cpu().numpy(), ref32), f"seed {seed} ELL"
+    assert_same_bits(out, ref32, f"seed {seed} ELL")
 
 
 @pytest.mark.parametrize("seed", range(16 * SCALE))
@@ -89,7 +91,7 @@ def test_fuzz_bsr(oracle, seed):
     ref = oracle.spmm_bsr(bsr.num_rows, br, bc, bsr.block_row_ptrs, bsr.block_col_idxs, bsr.data, b)
     out = padded_out(bsr.num_rows, n, rng)
     ops.spmm_bsr(ops.DeviceBSR.from_host(bsr), padded_device(b, rng), out=out, kernel=1)
-    assert np.array_equal(out.cpu().numpy(), ref), f"seed {seed} BSR {br}x{bc} Mb={mb} Kb={kb} N={n}"
+    assert_same_bits(out, ref, f"seed {seed} BSR {br}x{bc} Mb={mb} Kb={kb} N={n}")
 
 
 @pytest.mark.parametrize("seed", range(10 * SCALE))
@@ -119,8 +121,8 @@ def test_fuzz_bsr_mfma(oracle, seed):
         # four waves take a block row's blocks round-robin: rows of at most one block are a single fma chain and
         # match the FAST VALU chain bit for bit, every row is within the FAST bound and deterministic
         one_block = np.repeat(np.diff(np.array(ptrs)) <= 1, bd)
-        assert np.array_equal(mfma[one_block], valu[one_block]), f"seed {seed}: single-block rows must match the VALU chain"
-        assert np.array_equal(mfma, ops.spmm_bsr(a, bdev, kernel=2, acc="fast").cpu().numpy())
+        assert_same_bits(mfma[one_block], valu[one_block], f"seed {seed}: single-block rows must match the VALU chain")
+        assert_same_bits(mfma, ops.spmm_bsr(a, bdev, kernel=2, acc="fast"), f"seed {seed}: MFMA run twice")
         assert np.all(np.abs(mfma.astype(np.float64) - ref) <= 1e-5 * scale + 1e-30)
         assert np.all(np.abs(valu.astype(np.float64) - ref) <= 1e-5 * scale + 1e-30)
     a16 = synth.bf16_round(data.reshape(-1)).reshape(data.shape)
@@ -161,14 +163,14 @@ def test_fuzz_plan_order_and_general_entry_bet(oracle, seed):
     out = padded_out(m, n, rng)
     taken = ops._csr_plan(a, [bd], [out], "reference", None)
     if taken:
-        assert np.array_equal(out.cpu().numpy(), ref), f"seed {seed} plan order M={m} K={k} N={n}"
+        assert_same_bits(out, ref, f"seed {seed} plan order M={m} K={k} N={n}")
         outs = [padded_out(m, n, rng) for _ in range(2)]
         if outs[0].stride(0) == outs[1].stride(0):
             assert ops._csr_plan(a, [bd, bd], outs, "reference", None)
-            assert np.array_equal(outs[1].cpu().numpy(), ref), f"seed {seed} batched plan order"
+            assert_same_bits(outs[1], ref, f"seed {seed} batched plan order")
     out = padded_out(m, n, rng)
     ops.spmm_csr(a, bd, out=out, use_hint=False)              # general entry point: bets when nnz % M == 0
-    assert np.array_equal(out.cpu().numpy(), ref), f"seed {seed} general entry M={m} K={k} N={n} nnz={csr.nnz}"
+    assert_same_bits(out, ref, f"seed {seed} general entry M={m} K={k} N={n} nnz={csr.nnz}")
 
 
 @pytest.mark.parametrize("seed", range(8 * SCALE))

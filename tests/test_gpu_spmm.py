@@ -57,8 +57,9 @@ def random_csr(m, k, row_lens, seed):
 
 def test_row_stream_forced_on_small_and_odd_shapes():
     """row_stream.hpp (the persistent row-walking launch) forced on through the tuning build (MISPMM_STREAM=1): CSR with a
-    constant row length 9..16, ELL with padding, ragged workgroups, strided operands, plan order -- bit-exact against the
-    oracle in REFERENCE mode, within 1e-5 of sum|a||b| in FAST mode (tests/_row_stream_cases.py, a process of its own)."""
+    constant row length 9..16, ELL with padding, ragged workgroups, strided operands, plan order, the adversarial corpus's
+    order, signed-zero and poisoned cases -- bit-exact against the oracle in REFERENCE mode, within 1e-5 of sum|a||b| in FAST
+    mode (tests/_row_stream_cases.py, a process of its own)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,6 +69,7 @@ def test_row_stream_forced_on_small_and_odd_shapes():
                        env=dict(os.environ, MISPMM_LIB=tune, MISPMM_STREAM="1"))
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-2500:])
     assert "row_stream cases ok: 12" in p.stdout
+    assert "row_stream adversarial cases ok: 5" in p.stdout
 
 
 def test_production_library_never_takes_the_persistent_launch():
