@@ -74,6 +74,43 @@ extern "C" int mispmm_ell_compact_host(uint32_t M, uint32_t width, const uint32_
     return MISPMM_OK;
 }
 
+// fp64: the reference's column-major ELL straight into a row list in spmmELLCpu's order of addition, padding dropped.
+extern "C" int mispmm_ell_colmajor_to_rows_f64_host(uint32_t numRows, uint32_t numCols, uint32_t maxColNnz,
+                                                    const uint32_t *rowIdxs_host, const double *vals_host, uint32_t *nnz_out,
+                                                    uint32_t *rowPtrs_out_host, uint32_t *colIdxs_out_host, double *vals_out_host) {
+    if (!nnz_out) return fail(MISPMM_ERR_INVALID_ARG, "ell rows f64: nnz_out is null");
+    const size_t slots = static_cast<size_t>(numCols) * maxColNnz;
+    if (slots != 0 && (!rowIdxs_host || !vals_host)) return fail(MISPMM_ERR_INVALID_ARG, "ell rows f64: null input");
+    std::vector<uint32_t> fill(static_cast<size_t>(numRows) + 1, 0);
+    uint64_t count = 0;
+    for (size_t s = 0; s < slots; ++s) {
+        const uint32_t r = rowIdxs_host[s];
+        if (static_cast<int32_t>(r) < 0) continue;  // padding, as `if (row >= 0)` in spmm_ell.cpp:21
+        if (r >= numRows) return fail(MISPMM_ERR_INVALID_ARG, "ell rows f64: row index %u out of range", r);
+        ++fill[static_cast<size_t>(r) + 1];
+        ++count;
+    }
+    if (count > 0xFFFFFFFFull) return fail(MISPMM_ERR_INVALID_ARG, "ell rows f64: more than 2^32 entries");
+    *nnz_out = static_cast<uint32_t>(count);
+    if (!rowPtrs_out_host && !colIdxs_out_host && !vals_out_host) return MISPMM_OK;  // size query
+    if (!rowPtrs_out_host || (count != 0 && (!colIdxs_out_host || !vals_out_host)))
+        return fail(MISPMM_ERR_INVALID_ARG, "ell rows f64: null output");
+    for (uint32_t r = 0; r < numRows; ++r) fill[r + 1] += fill[r];
+    for (uint32_t r = 0; r <= numRows; ++r) rowPtrs_out_host[r] = fill[r];
+    // column-major walk, column then slot: each row receives its entries in the order the reference's CPU loop adds them
+    for (uint32_t c = 0; c < numCols; ++c) {
+        for (uint32_t s = 0; s < maxColNnz; ++s) {
+            const size_t i = static_cast<size_t>(c) * maxColNnz + s;
+            const uint32_t r = rowIdxs_host[i];
+            if (static_cast<int32_t>(r) < 0) continue;
+            const uint32_t o = fill[r]++;
+            colIdxs_out_host[o] = c;
+            vals_out_host[o] = vals_host[i];
+        }
+    }
+    return MISPMM_OK;
+}
+
 extern "C" int mispmm_shard_rows_by_nnz_host(uint32_t M, const uint32_t *rowPtrs_host, uint32_t parts,
                                              uint32_t *bounds_out_host) {
     if (parts == 0) return fail(MISPMM_ERR_INVALID_ARG, "shard: parts must be >= 1");
@@ -229,6 +266,42 @@ extern "C" int mispmm_bsr_nonzeros_host(uint32_t numBlockRows, uint32_t bR, uint
         }
     }
     if (n > 0xFFFFFFFFull) return fail(MISPMM_ERR_UNSUPPORTED, "bsr nonzeros: more than 2^32 entries");
+    if (fill) rowPtrs_out_host[static_cast<size_t>(numBlockRows) * bR] = static_cast<uint32_t>(n);
+    *nnz_out = static_cast<uint32_t>(n);
+    return MISPMM_OK;
+}
+
+// fp64 twin of mispmm_bsr_nonzeros_host: the same list in the same order, the values kept in double.
+extern "C" int mispmm_bsr_nonzeros_f64_host(uint32_t numBlockRows, uint32_t bR, uint32_t bC, uint32_t numBlocks,
+                                            const uint32_t *blockRowPtrs_host, const uint32_t *blockColIdxs_host,
+                                            const double *blocks_host, uint32_t *nnz_out, uint32_t *rowPtrs_out_host,
+                                            uint32_t *colIdxs_out_host, double *vals_out_host) {
+    if (!nnz_out) return fail(MISPMM_ERR_INVALID_ARG, "bsr nonzeros f64: nnz_out is null");
+    if (bR == 0 || bC == 0) return fail(MISPMM_ERR_INVALID_ARG, "bsr nonzeros f64: zero block dimension");
+    if (numBlockRows != 0 && !blockRowPtrs_host) return fail(MISPMM_ERR_INVALID_ARG, "bsr nonzeros f64: blockRowPtrs is null");
+    if (numBlocks != 0 && (!blockColIdxs_host || !blocks_host)) return fail(MISPMM_ERR_INVALID_ARG, "bsr nonzeros f64: null block arrays");
+    const bool fill = rowPtrs_out_host && colIdxs_out_host && vals_out_host;
+    if (!fill && (rowPtrs_out_host || colIdxs_out_host || vals_out_host))
+        return fail(MISPMM_ERR_INVALID_ARG, "bsr nonzeros f64: give all three outputs or none (size query)");
+    uint64_t n = 0;
+    for (uint32_t R = 0; R < numBlockRows; ++R) {
+        for (uint32_t i = 0; i < bR; ++i) {
+            if (fill) rowPtrs_out_host[static_cast<size_t>(R) * bR + i] = static_cast<uint32_t>(n);
+            for (uint32_t b = blockRowPtrs_host[R]; b < blockRowPtrs_host[R + 1]; ++b) {
+                if (b >= numBlocks) return fail(MISPMM_ERR_INVALID_ARG, "bsr nonzeros f64: block index %u out of range", b);
+                const double *row = blocks_host + (static_cast<size_t>(b) * bR + i) * bC;
+                for (uint32_t j = 0; j < bC; ++j) {
+                    if (row[j] == 0.0) continue;  // +0 and -0 alike: the term 0 * b cannot change a finite sum
+                    if (fill) {
+                        colIdxs_out_host[n] = blockColIdxs_host[b] * bC + j;
+                        vals_out_host[n] = row[j];
+                    }
+                    ++n;
+                }
+            }
+        }
+    }
+    if (n > 0xFFFFFFFFull) return fail(MISPMM_ERR_UNSUPPORTED, "bsr nonzeros f64: more than 2^32 entries");
     if (fill) rowPtrs_out_host[static_cast<size_t>(numBlockRows) * bR] = static_cast<uint32_t>(n);
     *nnz_out = static_cast<uint32_t>(n);
     return MISPMM_OK;

@@ -1,4 +1,4 @@
-// Vendor cross-check: rocSPARSE generic SpMM (alpha = 1, beta = 0, fp32 compute), in the role of
+// Vendor cross-check: rocSPARSE generic SpMM (alpha = 1, beta = 0, fp32 or fp64 compute), in the role of
 // the reference's cusparseTest (/root/reference/src/engine/cusparse.cu:9-57).  Same three timed
 // sections: prolog = handle + descriptors + buffer query + allocation + preprocess, kernel =
 // the compute stage + sync, epilog = teardown.  Not on the hot path and not captured in graphs
@@ -6,6 +6,7 @@
 #include <rocsparse/rocsparse.h>
 
 #include <chrono>
+#include <type_traits>
 
 #include "mispmm_internal.hpp"
 
@@ -37,10 +38,14 @@ struct VendorState {
             return fail(MISPMM_ERR_HIP, "%s failed with rocsparse_status %d (%s:%d)", #expr, (int)s_, __FILE__, __LINE__); \
     } while (0)
 
-extern "C" int mispmm_vendor_spmm_f32(mispmm_stream_t stream, int format, uint32_t M, uint32_t K, uint32_t nnz,
-                                      uint32_t block_dim, const uint32_t *ptrs_or_rows, const uint32_t *cols,
-                                      const float *vals, const float *B, uint32_t N, uint32_t ldb, float *C,
-                                      uint32_t ldc, double *pro_us, double *kernel_us, double *epi_us) {
+namespace {
+
+// T = float (rocsparse_datatype_f32_r) or double (f64_r): the same descriptors, algorithms and timed sections
+template <class T>
+int vendor_spmm(mispmm_stream_t stream, int format, uint32_t M, uint32_t K, uint32_t nnz, uint32_t block_dim,
+                const uint32_t *ptrs_or_rows, const uint32_t *cols, const T *vals, const T *B, uint32_t N, uint32_t ldb, T *C,
+                uint32_t ldc, double *pro_us, double *kernel_us, double *epi_us) {
+    constexpr rocsparse_datatype dt = std::is_same_v<T, double> ? rocsparse_datatype_f64_r : rocsparse_datatype_f32_r;
     using clock = std::chrono::high_resolution_clock;
     auto us = [](clock::time_point a, clock::time_point z) {
         return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(z - a).count() / 1000.0;
@@ -59,40 +64,40 @@ extern "C" int mispmm_vendor_spmm_f32(mispmm_stream_t stream, int format, uint32
         MISPMM_ROCSPARSE_TRY(rocsparse_create_handle(&v.handle));
         MISPMM_ROCSPARSE_TRY(rocsparse_set_stream(v.handle, st));
         rocsparse_spmm_alg alg = rocsparse_spmm_alg_default;
-        void *p0 = const_cast<uint32_t *>(ptrs_or_rows), *p1 = const_cast<uint32_t *>(cols), *pv = const_cast<float *>(vals);
+        void *p0 = const_cast<uint32_t *>(ptrs_or_rows), *p1 = const_cast<uint32_t *>(cols), *pv = const_cast<T *>(vals);
         if (format == MISPMM_VENDOR_CSR) {
             MISPMM_ROCSPARSE_TRY(rocsparse_create_csr_descr(&v.matA, M, K, nnz, p0, p1, pv, rocsparse_indextype_i32,
                                                             rocsparse_indextype_i32, rocsparse_index_base_zero,
-                                                            rocsparse_datatype_f32_r));
+                                                            dt));
             alg = rocsparse_spmm_alg_csr_row_split;
         } else if (format == MISPMM_VENDOR_COO) {
             MISPMM_ROCSPARSE_TRY(rocsparse_create_coo_descr(&v.matA, M, K, nnz, p0, p1, pv, rocsparse_indextype_i32,
-                                                            rocsparse_index_base_zero, rocsparse_datatype_f32_r));
+                                                            rocsparse_index_base_zero, dt));
             alg = rocsparse_spmm_alg_coo_segmented;
         } else {
             // block storage order: the reference's blocks are row-major inside (sparse_bsr.cu:138-155: CUSPARSE_ORDER_ROW)
             MISPMM_ROCSPARSE_TRY(rocsparse_create_bsr_descr(&v.matA, M / block_dim, K / block_dim, nnz, rocsparse_direction_row,
                                                             block_dim, p0, p1, pv, rocsparse_indextype_i32,
                                                             rocsparse_indextype_i32, rocsparse_index_base_zero,
-                                                            rocsparse_datatype_f32_r));
+                                                            dt));
             alg = rocsparse_spmm_alg_bsr;
         }
-        MISPMM_ROCSPARSE_TRY(rocsparse_create_dnmat_descr(&v.matB, K, N, ldb, const_cast<float *>(B), rocsparse_datatype_f32_r,
+        MISPMM_ROCSPARSE_TRY(rocsparse_create_dnmat_descr(&v.matB, K, N, ldb, const_cast<T *>(B), dt,
                                                           rocsparse_order_row));
-        MISPMM_ROCSPARSE_TRY(rocsparse_create_dnmat_descr(&v.matC, M, N, ldc, C, rocsparse_datatype_f32_r, rocsparse_order_row));
-        const float alpha = 1.f, beta = 0.f;
+        MISPMM_ROCSPARSE_TRY(rocsparse_create_dnmat_descr(&v.matC, M, N, ldc, C, dt, rocsparse_order_row));
+        const T alpha = 1, beta = 0;
         size_t buffer_size = 0;
         MISPMM_ROCSPARSE_TRY(rocsparse_spmm(v.handle, rocsparse_operation_none, rocsparse_operation_none, &alpha, v.matA, v.matB,
-                                            &beta, v.matC, rocsparse_datatype_f32_r, alg, rocsparse_spmm_stage_buffer_size,
+                                            &beta, v.matC, dt, alg, rocsparse_spmm_stage_buffer_size,
                                             &buffer_size, nullptr));
         MISPMM_HIP_TRY(hipMalloc(&v.buffer, buffer_size ? buffer_size : 4));
         MISPMM_ROCSPARSE_TRY(rocsparse_spmm(v.handle, rocsparse_operation_none, rocsparse_operation_none, &alpha, v.matA, v.matB,
-                                            &beta, v.matC, rocsparse_datatype_f32_r, alg, rocsparse_spmm_stage_preprocess,
+                                            &beta, v.matC, dt, alg, rocsparse_spmm_stage_preprocess,
                                             &buffer_size, v.buffer));
         MISPMM_HIP_TRY(hipStreamSynchronize(st));
         t2 = clock::now();
         MISPMM_ROCSPARSE_TRY(rocsparse_spmm(v.handle, rocsparse_operation_none, rocsparse_operation_none, &alpha, v.matA, v.matB,
-                                            &beta, v.matC, rocsparse_datatype_f32_r, alg, rocsparse_spmm_stage_compute,
+                                            &beta, v.matC, dt, alg, rocsparse_spmm_stage_compute,
                                             &buffer_size, v.buffer));
         MISPMM_HIP_TRY(hipStreamSynchronize(st));
         t3 = clock::now();
@@ -102,4 +107,20 @@ extern "C" int mispmm_vendor_spmm_f32(mispmm_stream_t stream, int format, uint32
     if (kernel_us) *kernel_us = us(t2, t3);
     if (epi_us) *epi_us = us(t3, t4);
     return MISPMM_OK;
+}
+
+}  // namespace
+
+extern "C" int mispmm_vendor_spmm_f32(mispmm_stream_t stream, int format, uint32_t M, uint32_t K, uint32_t nnz,
+                                      uint32_t block_dim, const uint32_t *ptrs_or_rows, const uint32_t *cols,
+                                      const float *vals, const float *B, uint32_t N, uint32_t ldb, float *C,
+                                      uint32_t ldc, double *pro_us, double *kernel_us, double *epi_us) {
+    return vendor_spmm<float>(stream, format, M, K, nnz, block_dim, ptrs_or_rows, cols, vals, B, N, ldb, C, ldc, pro_us, kernel_us, epi_us);
+}
+
+extern "C" int mispmm_vendor_spmm_f64(mispmm_stream_t stream, int format, uint32_t M, uint32_t K, uint32_t nnz,
+                                      uint32_t block_dim, const uint32_t *ptrs_or_rows, const uint32_t *cols,
+                                      const double *vals, const double *B, uint32_t N, uint32_t ldb, double *C,
+                                      uint32_t ldc, double *pro_us, double *kernel_us, double *epi_us) {
+    return vendor_spmm<double>(stream, format, M, K, nnz, block_dim, ptrs_or_rows, cols, vals, B, N, ldb, C, ldc, pro_us, kernel_us, epi_us);
 }

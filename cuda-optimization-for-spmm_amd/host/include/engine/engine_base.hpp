@@ -22,6 +22,7 @@ struct EngineOptions {
     int gatherMode = 1;      // mispmm_gather_mode of that run (default MISPMM_GATHER_TO_FIRST)
     int batch = 0;           // > 1 (`--batch n`, CSR): also multiply n dense operands by A in ONE launch (mispmm_csr_batch_f32)
     bool bf16 = false;       // `--dtype bf16` (BSR with 16-row blocks): also run the bf16 MFMA kernels (BASELINE config 4)
+    const char *recordDtype = nullptr;  // `--dtype fp64`: "fp64", printed with every record that carries no dtype of its own
 };
 EngineOptions &engineOptions();
 

@@ -34,4 +34,11 @@ template <typename DT, typename MT>
 DenseMatrix<DT, MT> *runWrapper(const WrapperShape &shape, int kernelNum, DenseMatrix<DT, MT> *b, DenseMatrix<DT, MT> *ref,
                                 const std::function<int(DT *, uint32_t, mispmm_stream_t)> &launch);
 
+// fp64, every format: its row list (rowPtrs[M+1], colIdxs, vals of listNnz entries, on the device) through mispmm_csr_f64,
+// one record.  Each format takes this path under one kernel number (fp64Kernel) and under MISPMM_KERNEL_AUTO; any other
+// number returns nullptr without a record (declined).
+DenseMatrix<double, uint32_t> *runF64(const char *format, uint32_t rows, uint32_t cols, uint32_t nnz, uint32_t listNnz, int kernelNum,
+                                      int fp64Kernel, const uint32_t *rowPtrs, const uint32_t *colIdxs, const double *vals,
+                                      DenseMatrix<double, uint32_t> *b, DenseMatrix<double, uint32_t> *ref, int acc);
+
 }  // namespace cuspmm

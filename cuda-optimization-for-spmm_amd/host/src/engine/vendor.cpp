@@ -10,8 +10,26 @@ template <typename DT, typename MT>
 bool vendorTest(SparseMatrix<DT, MT> *a, DenseMatrix<DT, MT> *b, DenseMatrix<DT, MT> *c, long &pro, long &kernel,
                 long &epi) {
     pro = kernel = epi = 0;
-    if constexpr (!std::is_same_v<DT, float>) {
-        return false;
+    if constexpr (std::is_same_v<DT, double>) {
+        // rocSPARSE in f64_r for CSR and COO
+        assert(a->onDevice && b->onDevice && c->onDevice);
+        b->toOrdering(ORDERING::ROW_MAJOR);
+        double p = 0, k = 0, e = 0;
+        int status;
+        if (auto *csr = dynamic_cast<SparseMatrixCSR<DT, MT> *>(a)) {
+            status = mispmm_vendor_spmm_f64(nullptr, MISPMM_VENDOR_CSR, csr->numRows, csr->numCols, csr->numNonZero, 0, csr->rowPtrs,
+                                            csr->colIdxs, csr->data, b->data, b->numCols, b->numCols, c->data, c->numCols, &p, &k, &e);
+        } else if (auto *coo = dynamic_cast<SparseMatrixCOO<DT, MT> *>(a)) {
+            status = mispmm_vendor_spmm_f64(nullptr, MISPMM_VENDOR_COO, coo->numRows, coo->numCols, coo->numNonZero, 0, coo->rowIdxs,
+                                            coo->colIdxs, coo->data, b->data, b->numCols, b->numCols, c->data, c->numCols, &p, &k, &e);
+        } else {
+            return false;
+        }
+        mispmmCheckError(status);
+        pro = (long)p;
+        kernel = (long)k;
+        epi = (long)e;
+        return true;
     } else {
         assert(a->onDevice && b->onDevice && c->onDevice);
         b->toOrdering(ORDERING::ROW_MAJOR);

@@ -106,6 +106,23 @@ template <typename DT, typename MT> SparseMatrixBSR<DT, MT> *SparseMatrixBSR<DT,
             d->nzSpansLong = longCount;
             d->nzSpansHybridOnly = hybridOnly;
         }
+    } else {
+        // fp64: the same non-zero list with the values kept in double (mispmm_csr_f64 multiplies from it); no span list
+        uint32_t nz = 0;
+        mispmmCheckError(mispmm_bsr_nonzeros_f64_host(this->numBlockRows, this->blockRowSize, this->blockColSize, this->numBlocks,
+                                                      this->blockRowPtrs, this->blockColIdxs, this->data, &nz, nullptr, nullptr, nullptr));
+        std::vector<uint32_t> rp((size_t)this->numRows + 1), ci(nz ? nz : 1);
+        std::vector<double> va(nz ? nz : 1);
+        mispmmCheckError(mispmm_bsr_nonzeros_f64_host(this->numBlockRows, this->blockRowSize, this->blockColSize, this->numBlocks,
+                                                      this->blockRowPtrs, this->blockColIdxs, this->data, &nz, rp.data(), ci.data(),
+                                                      va.data()));
+        d->nzCount = nz;
+        d->nzRowPtrs = allocateBuffer<MT>(rp.size(), true);
+        d->nzColIdxs = allocateBuffer<MT>(ci.size(), true);
+        d->nzVals = allocateBuffer<DT>(va.size(), true);
+        copyBuffer(d->nzRowPtrs, true, rp.data(), false, rp.size() * sizeof(MT));
+        copyBuffer(d->nzColIdxs, true, ci.data(), false, ci.size() * sizeof(MT));
+        copyBuffer(d->nzVals, true, va.data(), false, va.size() * sizeof(DT));
     }
     return d;
 }

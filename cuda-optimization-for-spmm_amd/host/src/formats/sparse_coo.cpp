@@ -76,6 +76,16 @@ template <typename DT, typename MT> SparseMatrixCOO<DT, MT> *SparseMatrixCOO<DT,
     copyBuffer(d->rowIdxs, true, rows, false, (size_t)this->numNonZero * sizeof(MT));
     copyBuffer(d->colIdxs, true, cols, false, (size_t)this->numNonZero * sizeof(MT));
     copyBuffer(d->data, true, vals, false, (size_t)this->numNonZero * sizeof(DT));
+    // fp64: the sorted entries are the row list mispmm_csr_f64 multiplies from; its row pointers come from the index-only
+    // boundary pass, run once here
+    if constexpr (std::is_same_v<DT, double>) {
+        if (this->numRows) {
+            mispmmCheckError(mispmm_coo_row_bounds(nullptr, this->numRows, this->numNonZero, d->rowIdxs, d->rowBoundsWorkspace));
+            mispmmCheckError(mispmm_device_sync());
+            d->rowBoundsReady = true;
+        }
+        return d;
+    }
     // long rows: the row boundaries of the sorted entries as spans, longest first (one counting pass per upload)
     if (this->numRows) {
         std::vector<uint32_t> rp((size_t)this->numRows + 1, 0);

@@ -101,6 +101,23 @@ template <typename DT, typename MT> SparseMatrixELL<DT, MT> *SparseMatrixELL<DT,
                 d->cpSpansHybridOnly = hybridOnly;
             }
         }
+    } else {
+        // fp64: the occupied slots straight from the column-major arrays as one row list, in spmmELLCpu's order
+        // (mispmm_csr_f64 multiplies from it); no padded view, no span list
+        uint32_t occupied = 0;
+        mispmmCheckError(mispmm_ell_colmajor_to_rows_f64_host(this->numRows, this->numCols, this->maxColNnz, this->rowIdxs, this->data,
+                                                              &occupied, nullptr, nullptr, nullptr));
+        std::vector<uint32_t> rp((size_t)this->numRows + 1), ci(occupied ? occupied : 1);
+        std::vector<double> va(occupied ? occupied : 1);
+        mispmmCheckError(mispmm_ell_colmajor_to_rows_f64_host(this->numRows, this->numCols, this->maxColNnz, this->rowIdxs, this->data,
+                                                              &occupied, rp.data(), ci.data(), va.data()));
+        d->cpRowPtrs = allocateBuffer<MT>(rp.size(), true);
+        d->cpColIdxs = allocateBuffer<MT>(ci.size(), true);
+        d->cpData = allocateBuffer<DT>(va.size(), true);
+        copyBuffer(d->cpRowPtrs, true, rp.data(), false, rp.size() * sizeof(MT));
+        copyBuffer(d->cpColIdxs, true, ci.data(), false, ci.size() * sizeof(MT));
+        copyBuffer(d->cpData, true, va.data(), false, va.size() * sizeof(DT));
+        d->cpCount = occupied;
     }
     return d;
 }

@@ -12,6 +12,8 @@
 //                    descriptor, sparse_bsr.cu:138-160, but never enables the check: engine_bsr.hpp:24)
 //   --save <file>    write the last result matrix as text
 //   --dtype <t>      fp32 (default) | bf16: with --bsr and 16-row blocks also run the bf16 MFMA kernels (BASELINE config 4)
+//                    | fp64: every selected format with double data and engines (files parsed as double); every record
+//                    carries "dtype":"fp64"; not with --gpus or --batch
 //   --gpus <n>       (--csr, --ell) also run the product row-sharded over n GPUs of this node: B replicated, C row slabs
 //                    gathered over xGMI; --gather first|peer|rccl|none picks how (default first = into device 0)
 //   --batch <n>      (--csr) also multiply n dense operands (n device copies of B) by A in ONE launch
@@ -42,7 +44,7 @@ static void printHelp(const char *prog) {
               << "  --no-vendor     Skip the rocSPARSE cross-check\n"
               << "  --vendor-bsr    rocSPARSE cross-check for --bsr as well (square blocks)\n"
               << "  --save <file>   Save the last result matrix\n"
-              << "  --dtype <t>     fp32 | bf16 (with --bsr, 16-row blocks: bf16 MFMA kernels as well)\n"
+              << "  --dtype <t>     fp32 | bf16 (with --bsr, 16-row blocks: bf16 MFMA kernels as well) | fp64 (double data)\n"
               << "  --gpus <n>      With --csr / --ell: also run row-sharded over n GPUs (B replicated, C slabs gathered)\n"
               << "  --batch <n>     With --csr: also multiply n dense operands by A in ONE launch (record key \"batch\")\n"
               << "  --gather <how>  first | peer | rccl | none (default first: slabs copied into device 0)\n"
@@ -51,7 +53,7 @@ static void printHelp(const char *prog) {
 
 int main(int argc, char *argv[]) {
     std::string dir, savePath, synthMode = "uniform";
-    bool wantCoo = false, wantCsr = false, wantBsr = false, wantEll = false, cpuOnly = false, vendorBsr = false;
+    bool wantCoo = false, wantCsr = false, wantBsr = false, wantEll = false, cpuOnly = false, vendorBsr = false, fp64 = false;
     int device = 0;
     long synthCols = 0;
     enum { OPT_DEVICE = 1000, OPT_SYNTH, OPT_ITERS, OPT_ACC, OPT_CPU, OPT_NOVENDOR, OPT_SAVE, OPT_VENDORBSR, OPT_GPUS, OPT_GATHER, OPT_DTYPE, OPT_BATCH };
@@ -96,8 +98,9 @@ int main(int argc, char *argv[]) {
             case OPT_DTYPE: {
                 const std::string t = optarg;
                 if (t == "bf16") cuspmm::engineOptions().bf16 = true;
+                else if (t == "fp64") fp64 = true;
                 else if (t != "fp32") {
-                    std::cerr << "Error: --dtype takes fp32 | bf16\n";
+                    std::cerr << "Error: --dtype takes fp32 | bf16 | fp64\n";
                     return EXIT_FAILURE;
                 }
                 break;
@@ -123,6 +126,11 @@ int main(int argc, char *argv[]) {
         printHelp(argv[0]);
         return EXIT_FAILURE;
     }
+    if (fp64 && (cuspmm::engineOptions().gpus > 0 || cuspmm::engineOptions().batch > 0)) {
+        std::cerr << "Error: --dtype fp64 runs on one GPU without batching: drop --gpus / --batch\n";
+        return EXIT_FAILURE;
+    }
+    if (fp64) cuspmm::engineOptions().recordDtype = "fp64";
 
     // inputs are found by suffix, as the reference does (main.cu:98-144)
     std::string cooFile, csrFile, bsrFile, denseFile, ellColind, ellValues, ellRowind, ellValuesCm;
@@ -170,7 +178,7 @@ int main(int argc, char *argv[]) {
 
     try {
         auto run = [&](auto *a, auto *engine) {
-            using Mat = cuspmm::DenseMatrix<float, uint32_t>;
+            using Mat = cuspmm::DenseMatrix<typename std::remove_pointer_t<decltype(a)>::DT, uint32_t>;
             Mat *dense = synthCols > 0 ? Mat::synthetic(a->numCols, (uint32_t)synthCols, 20241218, synthMode == "exact" ? 1 : 0)
                                        : new Mat(denseFile);
             cuspmm::runEngine(engine, a, dense, abs_tol, rel_tol, skipSeq, cpuOnly, savePath);
@@ -178,16 +186,22 @@ int main(int argc, char *argv[]) {
             delete engine;
             delete a;
         };
-        if (wantCoo) run(new cuspmm::SparseMatrixCOO<float, uint32_t>(cooFile), new cuspmm::EngineCOO<float, uint32_t, double>(dir));
-        if (wantCsr) run(new cuspmm::SparseMatrixCSR<float, uint32_t>(csrFile), new cuspmm::EngineCSR<float, uint32_t, double>(dir));
-        if (wantBsr) {
-            auto *a = new cuspmm::SparseMatrixBSR<float, uint32_t>(bsrFile);
-            auto *engine = new cuspmm::EngineBSR<float, uint32_t, double>(dir);
-            engine->SUPPORT_CUSPARSE = vendorBsr && a->blockRowSize == a->blockColSize;
-            run(a, engine);
-        }
-        if (wantEll)
-            run(new cuspmm::SparseMatrixELL<float, uint32_t>(ellRowind, ellValuesCm), new cuspmm::EngineELL<float, uint32_t, double>(dir));
+        // every selected format with DT data and engines (DT = double for --dtype fp64: the files are parsed as double)
+        auto runAll = [&](auto dtTag) {
+            using DT = decltype(dtTag);
+            if (wantCoo) run(new cuspmm::SparseMatrixCOO<DT, uint32_t>(cooFile), new cuspmm::EngineCOO<DT, uint32_t, double>(dir));
+            if (wantCsr) run(new cuspmm::SparseMatrixCSR<DT, uint32_t>(csrFile), new cuspmm::EngineCSR<DT, uint32_t, double>(dir));
+            if (wantBsr) {
+                auto *a = new cuspmm::SparseMatrixBSR<DT, uint32_t>(bsrFile);
+                auto *engine = new cuspmm::EngineBSR<DT, uint32_t, double>(dir);
+                engine->SUPPORT_CUSPARSE = vendorBsr && a->blockRowSize == a->blockColSize;
+                run(a, engine);
+            }
+            if (wantEll)
+                run(new cuspmm::SparseMatrixELL<DT, uint32_t>(ellRowind, ellValuesCm), new cuspmm::EngineELL<DT, uint32_t, double>(dir));
+        };
+        if (fp64) runAll(double{});
+        else runAll(float{});
     } catch (const std::exception &e) {
         std::cerr << "Error: " << e.what() << "\n";
         return EXIT_FAILURE;

@@ -39,8 +39,11 @@ DenseMatrix<DT, MT> *spmmBSRCpu(SparseMatrixBSR<DT, MT> *ma, DenseMatrix<DT, MT>
 template <typename DT, typename MT, typename AccT>
 DenseMatrix<DT, MT> *spmmBSRWrapper(int kernelNum, SparseMatrixBSR<DT, MT> *a, DenseMatrix<DT, MT> *b,
                                     DenseMatrix<DT, MT> *ref) {
-    if constexpr (!std::is_same_v<DT, float>) {
-        throw std::runtime_error("Not implemented");
+    if constexpr (std::is_same_v<DT, double>) {
+        // kernel 3, the zero-skipping slot: the non-zero list copy2Device built (mispmm_bsr_nonzeros_f64_host)
+        assert(a->onDevice && b->onDevice);
+        return runF64("BSR", a->numRows, a->numCols, a->numNonZero, a->nzCount, kernelNum, 3, a->nzRowPtrs, a->nzColIdxs, a->nzVals, b,
+                      ref, accModeOf<AccT>());
     } else {
         assert(a->onDevice && b->onDevice);
         b->toOrdering(ORDERING::ROW_MAJOR);

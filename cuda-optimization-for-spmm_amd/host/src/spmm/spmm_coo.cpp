@@ -26,8 +26,11 @@ DenseMatrix<DT, MT> *spmmCOOCpu(SparseMatrixCOO<DT, MT> *ma, DenseMatrix<DT, MT>
 template <typename DT, typename MT, typename AccT>
 DenseMatrix<DT, MT> *spmmCOOWrapper(int kernelNum, SparseMatrixCOO<DT, MT> *a, DenseMatrix<DT, MT> *b,
                                     DenseMatrix<DT, MT> *ref) {
-    if constexpr (!std::is_same_v<DT, float>) {
-        throw std::runtime_error("Not implemented");
+    if constexpr (std::is_same_v<DT, double>) {
+        // the row-sorted entries with the row boundaries copy2Device built
+        assert(a->onDevice && b->onDevice && (a->rowBoundsReady || a->numRows == 0));
+        return runF64("COO", a->numRows, a->numCols, a->numNonZero, a->numNonZero, kernelNum, 1, a->rowBoundsWorkspace, a->colIdxs,
+                      a->data, b, ref, accModeOf<AccT>());
     } else {
         assert(a->onDevice && b->onDevice);
         b->toOrdering(ORDERING::ROW_MAJOR);

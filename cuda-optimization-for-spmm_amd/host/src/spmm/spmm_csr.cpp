@@ -35,8 +35,10 @@ DenseMatrix<DT, MT> *spmmCSRCpu(SparseMatrixCSR<DT, MT> *ma, DenseMatrix<DT, MT>
 template <typename DT, typename MT, typename AccT>
 DenseMatrix<DT, MT> *spmmCSRWrapper(int kernelNum, SparseMatrixCSR<DT, MT> *a, DenseMatrix<DT, MT> *b,
                                     DenseMatrix<DT, MT> *ref) {
-    if constexpr (!std::is_same_v<DT, float>) {
-        throw std::runtime_error("Not implemented");  // like the reference, only float kernels exist
+    if constexpr (std::is_same_v<DT, double>) {
+        assert(a->onDevice && b->onDevice);
+        return runF64("CSR", a->numRows, a->numCols, a->numNonZero, a->numNonZero, kernelNum, 1, a->rowPtrs, a->colIdxs, a->data, b,
+                      ref, accModeOf<AccT>());
     } else {
         assert(a->onDevice && b->onDevice);
         b->toOrdering(ORDERING::ROW_MAJOR);  // untimed, on the device

@@ -35,8 +35,11 @@ DenseMatrix<DT, MT> *spmmELLCpu(SparseMatrixELL<DT, MT> *ma, DenseMatrix<DT, MT>
 template <typename DT, typename MT, typename AccT>
 DenseMatrix<DT, MT> *spmmELLWrapper(int kernelNum, SparseMatrixELL<DT, MT> *a, DenseMatrix<DT, MT> *b,
                                     DenseMatrix<DT, MT> *ref) {
-    if constexpr (!std::is_same_v<DT, float>) {
-        throw std::runtime_error("Not implemented");
+    if constexpr (std::is_same_v<DT, double>) {
+        // the occupied slots as copy2Device listed them (mispmm_ell_colmajor_to_rows_f64_host)
+        assert(a->onDevice && b->onDevice);
+        return runF64("ELL", a->numRows, a->numCols, a->numNonZero, a->cpCount, kernelNum, 1, a->cpRowPtrs, a->cpColIdxs, a->cpData, b,
+                      ref, accModeOf<AccT>());
     } else {
         assert(a->onDevice && b->onDevice);
         b->toOrdering(ORDERING::ROW_MAJOR);

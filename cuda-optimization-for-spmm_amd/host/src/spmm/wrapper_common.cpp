@@ -82,6 +82,23 @@ DenseMatrix<DT, MT> *runWrapper(const WrapperShape &shape, int kernelNum, DenseM
     return c;
 }
 
+DenseMatrix<double, uint32_t> *runF64(const char *format, uint32_t rows, uint32_t cols, uint32_t nnz, uint32_t listNnz, int kernelNum,
+                                      int fp64Kernel, const uint32_t *rowPtrs, const uint32_t *colIdxs, const double *vals,
+                                      DenseMatrix<double, uint32_t> *b, DenseMatrix<double, uint32_t> *ref, int acc) {
+    if (kernelNum != fp64Kernel && kernelNum != MISPMM_KERNEL_AUTO) return nullptr;
+    assert(b->onDevice);
+    b->toOrdering(ORDERING::ROW_MAJOR);
+    const double n = b->numCols;
+    WrapperShape shape{format, rows, cols, nnz, 2.0 * listNnz * n, listNnz * 12.0 + (rows + 1.0) * 4 + cols * n * 8 + rows * n * 8};
+    shape.dtype = "fp64";
+    return runWrapper<double, uint32_t>(shape, kernelNum, b, ref, [&](double *c, uint32_t ldc, mispmm_stream_t stream) {
+        return mispmm_csr_f64(stream, rows, cols, listNnz, rowPtrs, colIdxs, vals, b->data, b->numCols, b->numCols, c, ldc, acc);
+    });
+}
+
+template DenseMatrix<double, uint32_t> *runWrapper<double, uint32_t>(const WrapperShape &, int, DenseMatrix<double, uint32_t> *,
+                                                                   DenseMatrix<double, uint32_t> *,
+                                                                   const std::function<int(double *, uint32_t, mispmm_stream_t)> &);
 template DenseMatrix<float, uint32_t> *runWrapper<float, uint32_t>(const WrapperShape &, int, DenseMatrix<float, uint32_t> *,
                                                                  DenseMatrix<float, uint32_t> *,
                                                                  const std::function<int(float *, uint32_t, mispmm_stream_t)> &);

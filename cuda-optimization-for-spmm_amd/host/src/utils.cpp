@@ -26,7 +26,8 @@ void reportTime(const std::string &tc, uint32_t aNumRows, uint32_t aNumCols, uin
                     steady->iters, steady->usPerSpmm, steady->gflops, steady->hbmGBps, steady->rooflineFrac);
     }
     if (steady && steady->ngpus > 0) std::printf(",\n\"ngpus\":\"%d\"", steady->ngpus);
-    if (steady && steady->dtype) std::printf(",\n\"dtype\":\"%s\"", steady->dtype);
+    const char *dtype = steady && steady->dtype ? steady->dtype : cuspmm::engineOptions().recordDtype;
+    if (dtype) std::printf(",\n\"dtype\":\"%s\"", dtype);
     if (steady && steady->batch > 0) std::printf(",\n\"batch\":\"%d\"", steady->batch);
     if (steady && !steady->kernelTag.empty()) std::printf(",\n\"kernel\":\"%s\"", steady->kernelTag.c_str());
     std::printf("\n},\n");

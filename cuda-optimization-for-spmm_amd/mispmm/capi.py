@@ -86,6 +86,11 @@ SIGNATURES = {
     "mispmm_coo_sort_by_row_host": (_i, [_u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(_i)]),
     "mispmm_vendor_spmm_f32": (_i, [_vp, _i, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32,
                                     _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    "mispmm_csr_f64": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _i]),
+    "mispmm_ell_colmajor_to_rows_f64_host": (_i, [_u32, _u32, _u32, _vp, _vp, _c.POINTER(_u32), _vp, _vp, _vp]),
+    "mispmm_bsr_nonzeros_f64_host": (_i, [_u32, _u32, _u32, _u32, _vp, _vp, _vp, _c.POINTER(_u32), _vp, _vp, _vp]),
+    "mispmm_vendor_spmm_f64": (_i, [_vp, _i, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32,
+                                    _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
     "mispmm_dense_transpose_f32": (_i, [_vp, _u32, _u32, _vp, _vp]),
     "mispmm_f32_to_bf16": (_i, [_vp, _sz, _vp, _vp]),
     "mispmm_bf16_to_f32": (_i, [_vp, _sz, _vp, _vp]),

@@ -25,6 +25,16 @@ def _dev_f32(a, device):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
 
 
+def _dev_f64(a, device):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+
+
+def _check_dtype(dtype):
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"dtype must be torch.float32 or torch.float64, not {dtype}")
+    return dtype == torch.float64
+
+
 def _p(t):
     return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
 
@@ -193,12 +203,16 @@ class DeviceCSR:
     tuned: dict = field(default_factory=dict)   # (n, acc) -> (use the plan?, (storage-order us, plan-order us)) as measured by use_plan
 
     @staticmethod
-    def from_host(csr, device="cuda", spans=None, share_len=0, plan=None):
+    def from_host(csr, device="cuda", spans=None, share_len=0, plan=None, dtype=torch.float32):
         """spans: True / False to build the span list of the split kernel or not; None = when the mean row holds 24 entries
         or more (where the library's kernel 0 takes the split kernel).  share_len: rows longer than this are dealt to the 4
         waves of a workgroup (0 = the library's default, 128).  plan: True / False to keep a clustered row order or not;
         None = when the matrix has short rows (no span list), at least 1024 rows, and the clustering cuts the distinct
-        columns per row part by PLAN_MIN_GAIN or more (a once-per-upload analysis like the two above)."""
+        columns per row part by PLAN_MIN_GAIN or more (a once-per-upload analysis like the two above).
+        dtype=torch.float64: the host array's own values in double, for mispmm_csr_f64; no span list, no plan."""
+        if _check_dtype(dtype):
+            return DeviceCSR(csr.num_rows, csr.num_cols, csr.nnz, _dev_u32(csr.row_ptrs, device), _dev_u32(csr.col_idxs, device),
+                             _dev_f64(csr.data, device))
         hybrid_only = False
         if spans is None:
             spans, hybrid_only = wants_spans(csr.row_ptrs)
@@ -226,9 +240,14 @@ class DeviceELL:
     compact: tuple = None     # (nnz, rowPtrs, colIdxs, vals) of the occupied slots, when most of the ELL is padding
 
     @staticmethod
-    def from_host(ell, device="cuda", compact=None):
+    def from_host(ell, device="cuda", compact=None, dtype=torch.float32):
         """compact: True / False to list the occupied slots (mispmm_ell_compact_host) or not; None = when more than half of
-        the slots are padding."""
+        the slots are padding.  dtype=torch.float64: the occupied slots as a row list of doubles in spmmELLCpu's order of
+        addition (compact = that list, col_idxs / data its arrays), for mispmm_csr_f64."""
+        if _check_dtype(dtype):
+            rp, ci, va = ell_rows_f64(ell)
+            listed = (int(rp[-1]), _dev_u32(rp, device), _dev_u32(ci, device), _dev_f64(va, device), None)
+            return DeviceELL(ell.num_rows, ell.num_cols, int(np.diff(rp.astype(np.int64)).max(initial=0)), listed[2], listed[3], listed)
         if isinstance(ell, formats.ELLColMajor):
             ell = colmajor_ell_to_rowmajor(ell)
         cols = np.ascontiguousarray(ell.col_idxs, dtype=np.uint32).reshape(-1)
@@ -314,33 +333,66 @@ class DeviceCOO:
     col_idxs: torch.Tensor
     data: torch.Tensor
     spans: "RowSpans" = None     # long rows: (row, start, end, 0) per row, longest first -- carries the row boundaries
+    row_bounds: torch.Tensor = None   # float64 only: the (M+1) row boundaries of the sorted entries (mispmm_coo_row_bounds)
 
     @staticmethod
-    def from_host(coo, device="cuda"):
+    def from_host(coo, device="cuda", dtype=torch.float32):
         """Entries sorted by row only, a row's entries in storage order: the reference (spmm_coo.cpp) adds them into the row
-        in that order, so sorting them by column as well would change the fp32 sums."""
+        in that order, so sorting them by column as well would change the fp32 sums.  dtype=torch.float64: the values in
+        double and the row boundaries built once here, for mispmm_csr_f64; no span list."""
+        f64 = _check_dtype(dtype)
         order = np.argsort(np.asarray(coo.row_idxs), kind="stable")
         rows = np.asarray(coo.row_idxs)[order]
+        if f64:
+            a = DeviceCOO(coo.num_rows, coo.num_cols, coo.nnz, _dev_u32(rows, device), _dev_u32(np.asarray(coo.col_idxs)[order], device),
+                          _dev_f64(np.asarray(coo.data)[order], device))
+            a.row_bounds = coo_row_bounds(a)
+            return a
         row_ptrs = np.searchsorted(rows, np.arange(coo.num_rows + 1)).astype(np.uint32)
         return DeviceCOO(coo.num_rows, coo.num_cols, coo.nnz, _dev_u32(rows, device),
                          _dev_u32(coo.col_idxs[order], device), _dev_f32(coo.data[order], device), _row_spans(row_ptrs, device))
 
 
-def _out(m, n, b, out):
+def _out(m, n, b, out, dtype=torch.float32):
     if out is None:
-        out = torch.empty((m, n), dtype=torch.float32, device=b.device)
+        out = torch.empty((m, n), dtype=dtype, device=b.device)
     _require_gpu(out)
     if out.shape != (m, n):
         raise ValueError(f"out has shape {tuple(out.shape)}, expected {(m, n)}")
     return out
 
 
+def _dense_ld_f64(t):
+    if t.dim() != 2 or t.dtype != torch.float64 or t.stride(1) != 1 and t.shape[1] > 1:
+        raise ValueError("with a float64 A, dense operands must be 2-D float64 with unit column stride")
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+
+
+def _spmm_rows_f64(num_rows, num_cols, nnz, row_ptrs, col_idxs, data, b, out, kernel, acc, stream):
+    """fp64, every format: C = A @ B from A's row list through mispmm_csr_f64 (REFERENCE: fp64 product, fp64 add in list
+    order, bit-exact against the reference's CPU functions with DT = double)."""
+    if int(kernel) != 0:
+        raise ValueError("float64 operands have one kernel: kernel must be 0")
+    if b.shape[0] != num_cols:
+        raise ValueError(f"B has {b.shape[0]} rows, A has {num_cols} columns")
+    ldb = _dense_ld_f64(b)
+    n = b.shape[1]
+    c = _out(num_rows, n, b, out, torch.float64)
+    ldc = _dense_ld_f64(c)
+    capi.check(capi.lib().mispmm_csr_f64(_stream_ptr(stream), num_rows, num_cols, nnz, _p(row_ptrs), _p(col_idxs), _p(data), _p(b), n, ldb,
+                                         _p(c), ldc, capi.ACC_MODES[acc]))
+    return c
+
+
 def spmm_csr(a, b, out=None, kernel=0, acc="reference", stream=None, use_hint=True):
     """C = A @ B.  a: DeviceCSR, b: [K, N] float32 device tensor (row-major, any row stride).
     With the default kernel (0 / 5) a CSR whose rows all have the same length goes through
     mispmm_csr_uniform_f32 (no row-pointer fetch), one that carries `spans` (long rows) through mispmm_csr_split_f32 with
-    its rows longest first; use_hint=False forces the general entry point."""
+    its rows longest first; use_hint=False forces the general entry point.
+    A float64 A (DeviceCSR.from_host(..., dtype=torch.float64)) takes mispmm_csr_f64: B and out float64, kernel 0."""
     _require_gpu(a.row_ptrs, b)
+    if a.data.dtype == torch.float64:
+        return _spmm_rows_f64(a.num_rows, a.num_cols, a.nnz, a.row_ptrs, a.col_idxs, a.data, b, out, kernel, acc, stream)
     if b.shape[0] != a.num_cols:
         raise ValueError(f"B has {b.shape[0]} rows, A has {a.num_cols} columns")
     n = b.shape[1]
@@ -402,6 +454,8 @@ def spmm_csr_batch(a, bs, outs=None, acc="reference", stream=None):
     (mispmm_csr_batch_f32).  Returns the list of results."""
     if not bs:
         return []
+    if a.data.dtype == torch.float64:
+        raise ValueError("spmm_csr_batch multiplies float32 operands only; multiply a float64 A with spmm_csr")
     n, ldb = bs[0].shape[1], _dense_ld(bs[0])
     for b in bs:
         _require_gpu(b)
@@ -482,6 +536,9 @@ def spmm_csr_tiles(a, b, out=None, acc="reference", stream=None):
 
 def spmm_ell(a, b, out=None, kernel=0, acc="reference", stream=None):
     _require_gpu(a.col_idxs, b)
+    if a.data.dtype == torch.float64:
+        nnz, rp, ci, va, _ = a.compact
+        return _spmm_rows_f64(a.num_rows, a.num_cols, nnz, rp, ci, va, b, out, kernel, acc, stream)
     if b.shape[0] != a.num_cols:
         raise ValueError(f"B has {b.shape[0]} rows, A has {a.num_cols} columns")
     n = b.shape[1]
@@ -514,9 +571,13 @@ def spmm_bsr(a, b, out=None, kernel=0, acc="reference", stream=None):
     return c
 
 
-def bsr_nonzeros(bsr, device="cuda"):
+def bsr_nonzeros(bsr, device="cuda", dtype=torch.float32):
     """The non-zero block entries of a host BSR as a DeviceCSR in the reference's order of addition
-    (mispmm_bsr_nonzeros_host) -- the once-per-upload analysis step of the zero-skipping BSR path."""
+    (mispmm_bsr_nonzeros_host) -- the once-per-upload analysis step of the zero-skipping BSR path.  dtype=torch.float64:
+    the values in double (mispmm_bsr_nonzeros_f64_host), for mispmm_csr_f64; no span list."""
+    if _check_dtype(dtype):
+        rp, ci, va = bsr_nonzeros_f64_host(bsr)
+        return DeviceCSR(bsr.num_rows, bsr.num_cols, int(rp[-1]), _dev_u32(rp, device), _dev_u32(ci, device), _dev_f64(va, device))
     l = capi.lib()
     ptrs = np.ascontiguousarray(bsr.block_row_ptrs, dtype=np.uint32)
     cols = np.ascontiguousarray(bsr.block_col_idxs, dtype=np.uint32)
@@ -534,8 +595,11 @@ def bsr_nonzeros(bsr, device="cuda"):
 
 
 def spmm_bsr_nonzeros(nz, b, out=None, acc="reference", stream=None):
-    """C = A @ B from the non-zero list of a BSR (bsr_nonzeros): fp32 product, fp32 add in the reference's order."""
+    """C = A @ B from the non-zero list of a BSR (bsr_nonzeros): fp32 product, fp32 add in the reference's order.  A float64
+    list takes mispmm_csr_f64: B and out float64."""
     _require_gpu(nz.row_ptrs, b)
+    if nz.data.dtype == torch.float64:
+        return _spmm_rows_f64(nz.num_rows, nz.num_cols, nz.nnz, nz.row_ptrs, nz.col_idxs, nz.data, b, out, 0, acc, stream)
     if b.shape[0] != nz.num_cols:
         raise ValueError(f"B has {b.shape[0]} rows, A has {nz.num_cols} columns")
     n = b.shape[1]
@@ -558,8 +622,11 @@ def coo_row_bounds(a, stream=None):
 
 def spmm_coo(a, b, out=None, kernel=0, acc="reference", stream=None, workspace=True):
     """workspace=True allocates the (M+1)-entry row-boundary scratch; False uses binary search; a tensor from
-    coo_row_bounds() is used as is (pass kernel=2 to skip rebuilding it)."""
+    coo_row_bounds() is used as is (pass kernel=2 to skip rebuilding it).  A float64 A takes mispmm_csr_f64 over its row
+    boundaries: B and out float64, kernel 0."""
     _require_gpu(a.row_idxs, b)
+    if a.data.dtype == torch.float64:
+        return _spmm_rows_f64(a.num_rows, a.num_cols, a.nnz, a.row_bounds, a.col_idxs, a.data, b, out, kernel, acc, stream)
     if isinstance(workspace, torch.Tensor):
         ws = workspace
     else:
@@ -715,6 +782,43 @@ def colmajor_ell_to_rowmajor(ell):
                                                       vals.ctypes.data, ctypes.byref(width), cols.ctypes.data,
                                                       out.ctypes.data))
     return formats.ELLRowMajor(ell.num_rows, ell.num_cols, ell.nnz, w, cols, out)
+
+
+def ell_rows_f64(ell):
+    """(rowPtrs, colIdxs, vals float64) of a column-major ELL's occupied slots, every row in spmmELLCpu's order of addition
+    (mispmm_ell_colmajor_to_rows_f64_host).  A row-major ELL keeps its slot order, padding dropped."""
+    if isinstance(ell, formats.ELLRowMajor):
+        cols = np.ascontiguousarray(ell.col_idxs, dtype=np.uint32).reshape(ell.num_rows, -1)
+        vals = np.ascontiguousarray(ell.data, dtype=np.float64).reshape(ell.num_rows, -1)
+        live = cols != formats.ELL_PAD
+        rp = np.concatenate([[0], np.cumsum(live.sum(axis=1))]).astype(np.uint32)
+        return rp, cols[live], vals[live]
+    ridx = np.ascontiguousarray(ell.row_idxs, dtype=np.uint32)
+    vals = np.ascontiguousarray(ell.data, dtype=np.float64)
+    nnz = ctypes.c_uint32(0)
+    head = (ell.num_rows, ell.num_cols, ell.max_col_nnz, ridx.ctypes.data, vals.ctypes.data, ctypes.byref(nnz))
+    l = capi.lib()
+    capi.check(l.mispmm_ell_colmajor_to_rows_f64_host(*head, None, None, None))
+    rp = np.zeros(ell.num_rows + 1, np.uint32)
+    ci, va = np.zeros(max(nnz.value, 1), np.uint32), np.zeros(max(nnz.value, 1), np.float64)
+    capi.check(l.mispmm_ell_colmajor_to_rows_f64_host(*head, rp.ctypes.data, ci.ctypes.data, va.ctypes.data))
+    return rp, ci[:nnz.value], va[:nnz.value]
+
+
+def bsr_nonzeros_f64_host(bsr):
+    """(rowPtrs, colIdxs, vals float64) of a BSR's non-zero block entries in spmmBSRCpu's order (mispmm_bsr_nonzeros_f64_host)."""
+    ptrs = np.ascontiguousarray(bsr.block_row_ptrs, dtype=np.uint32)
+    cols = np.ascontiguousarray(bsr.block_col_idxs, dtype=np.uint32)
+    data = np.ascontiguousarray(bsr.data, dtype=np.float64).reshape(-1)
+    nnz = ctypes.c_uint32(0)
+    args = (bsr.num_block_rows, bsr.block_row_size, bsr.block_col_size, bsr.num_blocks, ptrs.ctypes.data, cols.ctypes.data,
+            data.ctypes.data, ctypes.byref(nnz))
+    l = capi.lib()
+    capi.check(l.mispmm_bsr_nonzeros_f64_host(*args, None, None, None))
+    rp = np.empty(bsr.num_rows + 1, dtype=np.uint32)
+    ci, va = np.empty(max(1, nnz.value), dtype=np.uint32), np.empty(max(1, nnz.value), dtype=np.float64)
+    capi.check(l.mispmm_bsr_nonzeros_f64_host(*args, rp.ctypes.data, ci.ctypes.data, va.ctypes.data))
+    return rp, ci[:nnz.value], va[:nnz.value]
 
 
 def shard_rows_by_nnz(row_ptrs, parts):

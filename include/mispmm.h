@@ -437,6 +437,41 @@ int mispmm_vendor_spmm_f32(mispmm_stream_t stream, int format, uint32_t M, uint3
                            uint32_t N, uint32_t ldb, float *C, uint32_t ldc, double *pro_us, double *kernel_us,
                            double *epi_us);
 
+/* -------------------------------------------------------------- fp64 x dense */
+/* C[M x N] = A[M x K] * B[K x N] in double precision, every format through ONE row list (rowPtrs[M+1], colIdxs, vals):
+ *   CSR  its own arrays;
+ *   COO  the entries in a STABLE sort by row (mispmm_coo_sort_by_row_host order) with rowPtrs from the index-only
+ *        mispmm_coo_row_bounds, run once at upload -- no fp64 COO entry point is needed;
+ *   ELL  mispmm_ell_colmajor_to_rows_f64_host (ascending column, then slot; padding dropped);
+ *   BSR  mispmm_bsr_nonzeros_f64_host (blocks in storage order, ascending column inside a block, zeros skipped).
+ * NUMERICS.  REFERENCE: C[r][j] = (((+0 + p1) + p2) + ...) + pL with p = a * b an fp64 product rounded once and every add
+ * rounded once, in list order, no FMA -- bit-exact against spmmCSRCpu with AccT = double and against spmmCOOCpu /
+ * spmmELLCpu / spmmBSRCpu adding into a zeroed C, whose arithmetic is the same.  FAST: an fp64 fma chain in the same order,
+ * |c - ref| <= 1e-12 * sum |a||b| per element; never -0.  A padding or dead slot adds 0 * 0 = +0 to a sum that started at
+ * +0 and is never -0: exact.  BSR list exception (as for mispmm_bsr_nonzeros_f32): a skipped explicit zero of A never forms
+ * 0 * Inf.
+ * Any M, K, nnz, N, ragged and empty rows, any ldb / ldc >= N: 16-byte lanes where N, ldb, ldc are even and B, C 16-byte
+ * aligned, else 8-byte lanes; a B or C of 2 GiB or more takes a 64-bit-address body.  Validates its arguments before any
+ * device work; M == 0 or N == 0 is a no-op.  No allocation, no synchronisation: capturable.  mispmm_last_kernel() = csr_f64<...>. */
+int mispmm_csr_f64(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs, const uint32_t *colIdxs,
+                   const double *vals, const double *B, uint32_t N, uint32_t ldb, double *C, uint32_t ldc, int acc_mode);
+/* HOST helper: the reference's column-major ELL (rowIdxs_host / vals_host [numCols x maxColNnz], padding row index
+ * 0xFFFFFFFF) straight into the row list, every row's entries in the order spmmELLCpu adds them (ascending column, then
+ * slot), padding dropped.  Call with the three outputs NULL for *nnz_out, then with rowPtrs_out[numRows + 1] and arrays
+ * of *nnz_out entries. */
+int mispmm_ell_colmajor_to_rows_f64_host(uint32_t numRows, uint32_t numCols, uint32_t maxColNnz, const uint32_t *rowIdxs_host,
+                                         const double *vals_host, uint32_t *nnz_out, uint32_t *rowPtrs_out_host,
+                                         uint32_t *colIdxs_out_host, double *vals_out_host);
+/* HOST helper: the fp64 twin of mispmm_bsr_nonzeros_host (same list, same order, same size query). */
+int mispmm_bsr_nonzeros_f64_host(uint32_t numBlockRows, uint32_t bR, uint32_t bC, uint32_t numBlocks,
+                                 const uint32_t *blockRowPtrs_host, const uint32_t *blockColIdxs_host, const double *blocks_host,
+                                 uint32_t *nnz_out, uint32_t *rowPtrs_out_host, uint32_t *colIdxs_out_host, double *vals_out_host);
+/* rocSPARSE generic SpMM in f64_r: the argument list, formats (CSR, COO) and timing of mispmm_vendor_spmm_f32. */
+int mispmm_vendor_spmm_f64(mispmm_stream_t stream, int format, uint32_t M, uint32_t K, uint32_t nnz, uint32_t block_dim,
+                           const uint32_t *ptrs_or_rows, const uint32_t *cols, const double *vals, const double *B,
+                           uint32_t N, uint32_t ldb, double *C, uint32_t ldc, double *pro_us, double *kernel_us,
+                           double *epi_us);
+
 /* ------------------------------------------------------------ dense helpers */
 /* dst[cols x rows] = transpose(src[rows x cols]); both dense row-major buffers.
  * Replaces the host round trip of DenseMatrix::toOrdering (dense.cu:139-191). */
