@@ -635,3 +635,45 @@ extern "C" int mispmm_csr_tiles_host(uint32_t M, uint32_t K, const uint32_t *row
     *numListed_out = static_cast<uint32_t>(listedTotal);
     return MISPMM_OK;
 }
+
+// ---- B panels (mispmm_csr_panel_f32): per row, where its entries of each panel of `panelRows` consecutive B rows start.
+// Row-major, numPanels + 1 offsets per row: the kernel's lane group reads offset p + 1 of its row while it sums panel p.  One
+// pass over the entries; a row must ascend strictly, or walking the panels in order would not be its storage order.
+extern "C" int mispmm_csr_panels_host(uint32_t M, uint32_t K, const uint32_t *rowPtrs_host, const uint32_t *colIdxs_host, uint32_t panelRows,
+                                      uint32_t *numPanels_out, uint64_t *numOffsets_out, uint32_t *panelPtrs_out_host,
+                                      uint64_t panelPtrs_capacity) {
+    if (!rowPtrs_host || !numPanels_out || !numOffsets_out) return fail(MISPMM_ERR_INVALID_ARG, "csr_panels: null pointer");
+    if (panelRows == 0) return fail(MISPMM_ERR_INVALID_ARG, "csr_panels: panels of at least one B row");
+    if ((panelPtrs_out_host != nullptr) != (panelPtrs_capacity != 0))
+        return fail(MISPMM_ERR_INVALID_ARG, "csr_panels: panelPtrs and its capacity go together (both for a fill, neither for a size query)");
+    const uint32_t numPanels = static_cast<uint32_t>(ceil_div64(K, panelRows));
+    const uint64_t numOffsets = static_cast<uint64_t>(M) * (static_cast<uint64_t>(numPanels) + 1u);
+    for (uint32_t r = 0; r < M; ++r)
+        if (rowPtrs_host[r + 1] < rowPtrs_host[r]) return fail(MISPMM_ERR_INVALID_ARG, "csr_panels: rowPtrs decrease at row %u", r);
+    const uint64_t nnz = rowPtrs_host[M];
+    if (nnz != 0 && !colIdxs_host) return fail(MISPMM_ERR_INVALID_ARG, "csr_panels: colIdxs is null");
+    for (uint64_t i = 0; i < nnz; ++i)
+        if (colIdxs_host[i] >= K) return fail(MISPMM_ERR_INVALID_ARG, "csr_panels: column index %u out of range", colIdxs_host[i]);
+    for (uint32_t r = 0; r < M; ++r)
+        for (uint32_t i = rowPtrs_host[r] + 1; i < rowPtrs_host[r + 1]; ++i)
+            if (colIdxs_host[i] <= colIdxs_host[i - 1])
+                return fail(MISPMM_ERR_UNSUPPORTED, "csr_panels: the columns of row %u do not ascend (panels are walked in column order)", r);
+    *numPanels_out = numPanels;
+    *numOffsets_out = numOffsets;
+    if (!panelPtrs_out_host) return MISPMM_OK;
+    if (panelPtrs_capacity < numOffsets)
+        return fail(MISPMM_ERR_INVALID_ARG, "csr_panels: panelPtrs holds %llu offsets, %llu are needed",
+                    static_cast<unsigned long long>(panelPtrs_capacity), static_cast<unsigned long long>(numOffsets));
+    for (uint32_t r = 0; r < M; ++r) {
+        uint32_t *pp = panelPtrs_out_host + static_cast<uint64_t>(r) * (numPanels + 1u);
+        uint32_t i = rowPtrs_host[r];
+        const uint32_t stop = rowPtrs_host[r + 1];
+        for (uint32_t p = 0; p < numPanels; ++p) {
+            pp[p] = i;
+            const uint64_t limit = (static_cast<uint64_t>(p) + 1u) * panelRows;  // first column of the next panel
+            while (i < stop && colIdxs_host[i] < limit) ++i;
+        }
+        pp[numPanels] = stop;
+    }
+    return MISPMM_OK;
+}

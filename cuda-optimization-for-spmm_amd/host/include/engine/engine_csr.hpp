@@ -27,6 +27,12 @@ bool spmmCSRMultiGpu(int ngpus, int gatherMode, SparseMatrixCSR<DT, MT> *a, Dens
 template <typename DT, typename MT, typename AccT>
 bool spmmCSRBatched(int batch, SparseMatrixCSR<DT, MT> *a, DenseMatrix<DT, MT> *b, DenseMatrix<DT, MT> *ref);
 
+// `--panels`: the panel offsets are built here from the HOST matrix (mispmm_csr_panels_host; copy2Device never builds them), then
+// the panel-tiled LDS kernel (mispmm_csr_panel_f32) multiplies from the device matrix's own arrays; one record with
+// kernelType 7.  A matrix the builder declines prints one line to stderr, adds no record and returns false.
+template <typename DT, typename MT, typename AccT>
+bool spmmCSRPanels(SparseMatrixCSR<DT, MT> *hostA, SparseMatrixCSR<DT, MT> *a, DenseMatrix<DT, MT> *b, DenseMatrix<DT, MT> *ref);
+
 #define CUSPMM_DECLARE_CSR_WRAPPER(N)                                                                          \
     template <typename DT, typename MT, typename AccT>                                                         \
     DenseMatrix<DT, MT> *spmmCSRWrapper##N(SparseMatrixCSR<DT, MT> *a, DenseMatrix<DT, MT> *b,                 \

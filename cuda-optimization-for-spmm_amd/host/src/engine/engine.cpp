@@ -66,6 +66,12 @@ void runEngine(EngT *engine, typename EngT::MataT *a, typename EngT::MatbT *b, f
                 spmmCSRBatched<typename ma_t::DT, typename ma_t::MT, double>(engineOptions().batch, da, db, cpuRes);
         }
 
+        // 3d. `--panels`: the panel-tiled LDS kernel for dense-regime matrices (CSR, fp32), an explicit alternative no kernel id
+        //     or dispatcher selects: one more record, kernelType 7
+        if constexpr (std::is_same_v<ma_t, SparseMatrixCSR<typename ma_t::DT, typename ma_t::MT>>) {
+            if (engineOptions().panels) spmmCSRPanels<typename ma_t::DT, typename ma_t::MT, double>(a, da, db, cpuRes);
+        }
+
         // 4. vendor library, timed AND compared (the reference hard-codes correct = 1, engine.cpp:47-55)
         if (engine->SUPPORT_CUSPARSE && engineOptions().vendorCheck) {
             mb_t *dc = new mb_t(a->numRows, b->numCols, true, ORDERING::ROW_MAJOR);

@@ -18,6 +18,9 @@
 //                    gathered over xGMI; --gather first|peer|rccl|none picks how (default first = into device 0)
 //   --batch <n>      (--csr) also multiply n dense operands (n device copies of B) by A in ONE launch
 //                    (mispmm_csr_batch_f32): one more record, key "batch", steady-state figures per product
+//   --panels         (--csr) also run the panel-tiled LDS kernel (mispmm_csr_panel_f32, for dense-regime matrices: B staged in
+//                    LDS panel by panel) once: one more record, "kernelType":"7"; a matrix whose rows do not ascend in column
+//                    is declined with one line on stderr and no record; needs --csr, not with --dtype fp64 or --gpus
 #include <getopt.h>
 
 #include <cstdlib>
@@ -47,6 +50,7 @@ static void printHelp(const char *prog) {
               << "  --dtype <t>     fp32 | bf16 (with --bsr, 16-row blocks: bf16 MFMA kernels as well) | fp64 (double data)\n"
               << "  --gpus <n>      With --csr / --ell: also run row-sharded over n GPUs (B replicated, C slabs gathered)\n"
               << "  --batch <n>     With --csr: also multiply n dense operands by A in ONE launch (record key \"batch\")\n"
+              << "  --panels        With --csr: also run the panel-tiled LDS kernel (B staged in LDS; record kernelType 7)\n"
               << "  --gather <how>  first | peer | rccl | none (default first: slabs copied into device 0)\n"
               << "  -h, --help      Display this help message\n";
 }
@@ -56,7 +60,7 @@ int main(int argc, char *argv[]) {
     bool wantCoo = false, wantCsr = false, wantBsr = false, wantEll = false, cpuOnly = false, vendorBsr = false, fp64 = false;
     int device = 0;
     long synthCols = 0;
-    enum { OPT_DEVICE = 1000, OPT_SYNTH, OPT_ITERS, OPT_ACC, OPT_CPU, OPT_NOVENDOR, OPT_SAVE, OPT_VENDORBSR, OPT_GPUS, OPT_GATHER, OPT_DTYPE, OPT_BATCH };
+    enum { OPT_DEVICE = 1000, OPT_SYNTH, OPT_ITERS, OPT_ACC, OPT_CPU, OPT_NOVENDOR, OPT_SAVE, OPT_VENDORBSR, OPT_GPUS, OPT_GATHER, OPT_DTYPE, OPT_BATCH, OPT_PANELS };
     const option longOpts[] = {{"bsr", no_argument, nullptr, 'B'},           {"coo", no_argument, nullptr, 'O'},
                                {"csr", no_argument, nullptr, 'S'},           {"ell", no_argument, nullptr, 'E'},
                                {"cuda", no_argument, nullptr, 'U'},          {"help", no_argument, nullptr, 'h'},
@@ -70,6 +74,7 @@ int main(int argc, char *argv[]) {
                                {"vendor-bsr", no_argument, nullptr, OPT_VENDORBSR},
                                {"gpus", required_argument, nullptr, OPT_GPUS},
                                {"batch", required_argument, nullptr, OPT_BATCH},
+                               {"panels", no_argument, nullptr, OPT_PANELS},
                                {"gather", required_argument, nullptr, OPT_GATHER},
                                {"dtype", required_argument, nullptr, OPT_DTYPE},
                                {nullptr, 0, nullptr, 0}};
@@ -107,6 +112,7 @@ int main(int argc, char *argv[]) {
             }
             case OPT_GPUS: cuspmm::engineOptions().gpus = std::atoi(optarg); break;
             case OPT_BATCH: cuspmm::engineOptions().batch = std::atoi(optarg); break;
+            case OPT_PANELS: cuspmm::engineOptions().panels = true; break;
             case OPT_GATHER: {
                 const std::string g = optarg;
                 if (g == "none") cuspmm::engineOptions().gatherMode = MISPMM_GATHER_NONE;
@@ -128,6 +134,14 @@ int main(int argc, char *argv[]) {
     }
     if (fp64 && (cuspmm::engineOptions().gpus > 0 || cuspmm::engineOptions().batch > 0)) {
         std::cerr << "Error: --dtype fp64 runs on one GPU without batching: drop --gpus / --batch\n";
+        return EXIT_FAILURE;
+    }
+    if (cuspmm::engineOptions().panels && !wantCsr) {
+        std::cerr << "Error: --panels is the panel kernel of the CSR engine: it needs --csr\n";
+        return EXIT_FAILURE;
+    }
+    if (cuspmm::engineOptions().panels && (fp64 || cuspmm::engineOptions().gpus > 0)) {
+        std::cerr << "Error: --panels is the fp32 single-GPU panel kernel: drop --dtype fp64 / --gpus\n";
         return EXIT_FAILURE;
     }
     if (fp64) cuspmm::engineOptions().recordDtype = "fp64";

@@ -174,6 +174,43 @@ bool spmmCSRBatched(int batch, SparseMatrixCSR<DT, MT> *a, DenseMatrix<DT, MT> *
     }
 }
 
+template <typename DT, typename MT, typename AccT>
+bool spmmCSRPanels(SparseMatrixCSR<DT, MT> *hostA, SparseMatrixCSR<DT, MT> *a, DenseMatrix<DT, MT> *b, DenseMatrix<DT, MT> *ref) {
+    if constexpr (!std::is_same_v<DT, float>) {
+        throw std::runtime_error("Not implemented");
+    } else {
+        assert(!hostA->onDevice && a->onDevice && b->onDevice);
+        b->toOrdering(ORDERING::ROW_MAJOR);
+        const uint32_t M = a->numRows, K = a->numCols, panelRows = mispmm_csr_panel_rows();
+        uint32_t numPanels = 0;
+        uint64_t numOffsets = 0;
+        int st = mispmm_csr_panels_host(M, K, hostA->rowPtrs, hostA->colIdxs, panelRows, &numPanels, &numOffsets, nullptr, 0);
+        if (st == MISPMM_ERR_UNSUPPORTED) {
+            std::cerr << "--panels: matrix declined (" << mispmm_last_error() << "), no record\n";
+            return false;
+        }
+        mispmmCheckError(st);
+        std::vector<uint32_t> host((size_t)std::max<uint64_t>(numOffsets, 1));
+        mispmmCheckError(mispmm_csr_panels_host(M, K, hostA->rowPtrs, hostA->colIdxs, panelRows, &numPanels, &numOffsets, host.data(), host.size()));
+        uint32_t *panelPtrs = allocateBuffer<uint32_t>(host.size(), true);
+        copyBuffer(panelPtrs, true, host.data(), false, host.size() * sizeof(uint32_t));
+        const double n = b->numCols;
+        // algorithmic bytes of THIS kernel: its row structure is the panel offsets, not the row pointers (the panels of B that
+        // every 64-row block stages again come out of L2 and are not counted: DESIGN.md section 4)
+        const WrapperShape shape{"CSR", M, K, a->numNonZero, 2.0 * a->numNonZero * n,
+                                 a->numNonZero * 8.0 + (double)numOffsets * 4 + K * n * 4 + M * n * 4};
+        const int acc = accModeOf<AccT>();
+        auto *res = runWrapper<DT, MT>(shape, 7, b, ref, [&](float *c, uint32_t ldc, mispmm_stream_t stream) {
+            return mispmm_csr_panel_f32(stream, M, K, a->numNonZero, a->rowPtrs, a->colIdxs, a->data, panelPtrs, panelRows, b->data,
+                                        b->numCols, b->numCols, c, ldc, acc);
+        });
+        releaseBuffer(panelPtrs, true);
+        const bool ran = res != nullptr;
+        delete res;
+        return ran;
+    }
+}
+
 #define CUSPMM_INST(DT)                                                                                              \
     template DenseMatrix<DT, uint32_t> *spmmCSRCpu<DT, uint32_t, double>(SparseMatrixCSR<DT, uint32_t> *,           \
                                                                          DenseMatrix<DT, uint32_t> *,               \
@@ -188,6 +225,10 @@ template bool spmmCSRBatched<float, uint32_t, double>(int, SparseMatrixCSR<float
                                                       DenseMatrix<float, uint32_t> *);
 template bool spmmCSRBatched<double, uint32_t, double>(int, SparseMatrixCSR<double, uint32_t> *, DenseMatrix<double, uint32_t> *,
                                                        DenseMatrix<double, uint32_t> *);
+template bool spmmCSRPanels<float, uint32_t, double>(SparseMatrixCSR<float, uint32_t> *, SparseMatrixCSR<float, uint32_t> *,
+                                                     DenseMatrix<float, uint32_t> *, DenseMatrix<float, uint32_t> *);
+template bool spmmCSRPanels<double, uint32_t, double>(SparseMatrixCSR<double, uint32_t> *, SparseMatrixCSR<double, uint32_t> *,
+                                                      DenseMatrix<double, uint32_t> *, DenseMatrix<double, uint32_t> *);
 template DenseMatrix<float, uint32_t> *spmmCSRCpu<float, uint32_t, float>(SparseMatrixCSR<float, uint32_t> *,
                                                                          DenseMatrix<float, uint32_t> *,
                                                                          DenseMatrix<float, uint32_t> *);

@@ -534,6 +534,49 @@ def spmm_csr_tiles(a, b, out=None, acc="reference", stream=None):
     return c
 
 
+@dataclass
+class DeviceCSRPanels:
+    """A CSR plus, per row, where its entries of each panel of `panel_rows` consecutive B rows start (mispmm_csr_panels_host):
+    what mispmm_csr_panel_f32 walks.  The entries stay in the matrix's own order; rows must ascend in column."""
+    num_rows: int
+    num_cols: int
+    nnz: int
+    panel_rows: int
+    num_panels: int
+    row_ptrs: torch.Tensor
+    col_idxs: torch.Tensor
+    data: torch.Tensor
+    panel_ptrs: torch.Tensor     # num_rows x (num_panels + 1) offsets into col_idxs / data, row-major
+
+    @staticmethod
+    def from_host(csr, device="cuda", panel_rows=None):
+        """Raises capi.MispmmError for a matrix the builder declines (a row whose columns do not ascend: ERR_UNSUPPORTED)."""
+        l = capi.lib()
+        depth = int(panel_rows) if panel_rows is not None else l.mispmm_csr_panel_rows()
+        rp = np.ascontiguousarray(csr.row_ptrs, dtype=np.uint32)
+        ci = np.ascontiguousarray(csr.col_idxs, dtype=np.uint32)
+        npan, noff = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        head = (csr.num_rows, csr.num_cols, rp.ctypes.data, ci.ctypes.data, depth, ctypes.byref(npan), ctypes.byref(noff))
+        capi.check(l.mispmm_csr_panels_host(*head, None, 0))
+        pp = np.zeros(max(noff.value, 1), np.uint32)
+        capi.check(l.mispmm_csr_panels_host(*head, pp.ctypes.data, pp.shape[0]))
+        return DeviceCSRPanels(csr.num_rows, csr.num_cols, csr.nnz, depth, npan.value, _dev_u32(rp, device), _dev_u32(ci, device),
+                               _dev_f32(csr.data, device), _dev_u32(pp, device))
+
+
+def spmm_csr_panels(a, b, out=None, acc="reference", stream=None):
+    """C = A @ B with B staged panel by panel in LDS (mispmm_csr_panel_f32, for dense-regime A): a: DeviceCSRPanels."""
+    _require_gpu(a.panel_ptrs, b)
+    if b.shape[0] != a.num_cols:
+        raise ValueError(f"B has {b.shape[0]} rows, A has {a.num_cols} columns")
+    n = b.shape[1]
+    c = _out(a.num_rows, n, b, out)
+    capi.check(capi.lib().mispmm_csr_panel_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs),
+                                               _p(a.data), _p(a.panel_ptrs), a.panel_rows, _p(b), n, _dense_ld(b), _p(c), _dense_ld(c),
+                                               capi.ACC_MODES[acc]))
+    return c
+
+
 def spmm_ell(a, b, out=None, kernel=0, acc="reference", stream=None):
     _require_gpu(a.col_idxs, b)
     if a.data.dtype == torch.float64:

@@ -254,6 +254,31 @@ int mispmm_csr_lds_tile_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint
                             const float *vals, const uint32_t *rowMap, const float *B, uint32_t N, uint32_t ldb, float *C, uint32_t ldc,
                             int acc_mode);
 
+/* B panels in LDS, for the DENSE regime (a B row re-read by hundreds of rows of A, e.g. the 2048 x 2048 density 0.1 .. 0.9
+ * sweep of the reference's test/sparsity.sh): stands in for the shared-memory kernel src/spmm/csr/spmm_csr_k4.cu:26-79.  B is
+ * walked in panels of `panelRows` consecutive rows; a workgroup stages each panel once (double-buffered LDS-DMA) for its 64 rows
+ * of A x 64 columns and sums every row's entries of the panel from LDS.  An explicit alternative: no
+ * dispatcher picks it.
+ *   mispmm_csr_panel_rows   the panel depth to build for (MISPMM_PANEL_ROWS; the tuning build's MISPMM_PANEL_P knob: 64 | 128).
+ *   mispmm_csr_panels_host  HOST, once per upload: panelPtrs[r * (numPanels + 1) + p] = the offset in colIdxs / vals at which
+ *                           row r's entries of panel p start, numPanels = ceil(K / panelRows); entry numPanels of a row is
+ *                           rowPtrs[r + 1].  panelPtrs_out_host NULL and capacity 0 = size query (*numPanels_out,
+ *                           *numOffsets_out = M * (numPanels + 1)); both given = fill (capacity in elements, >= *numOffsets_out);
+ *                           one without the other is MISPMM_ERR_INVALID_ARG, as are decreasing row pointers and a column >= K.
+ *                           A row whose columns do not ascend strictly is MISPMM_ERR_UNSUPPORTED: panels ascend, so only an
+ *                           ascending row is summed in storage order (the REFERENCE contract).
+ *   mispmm_csr_panel_f32    C = A * B from the matrix's own arrays plus panelPtrs; REFERENCE mode bit-exact.  Any M, K, ragged
+ *                           and empty rows; N a multiple of 4 with 16-byte-aligned B, C, ldb, ldc; B, C and the entry arrays
+ *                           below 2 GiB; panelRows 64 or 128 and the depth panelPtrs was built with -- anything else is
+ *                           MISPMM_ERR_UNSUPPORTED.  Launches and does nothing else (graph-capturable). */
+#define MISPMM_PANEL_ROWS 128u
+uint32_t mispmm_csr_panel_rows(void);
+int mispmm_csr_panels_host(uint32_t M, uint32_t K, const uint32_t *rowPtrs_host, const uint32_t *colIdxs_host, uint32_t panelRows,
+                           uint32_t *numPanels_out, uint64_t *numOffsets_out, uint32_t *panelPtrs_out_host, uint64_t panelPtrs_capacity);
+int mispmm_csr_panel_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs, const uint32_t *colIdxs,
+                         const float *vals, const uint32_t *panelPtrs, uint32_t panelRows, const float *B, uint32_t N, uint32_t ldb,
+                         float *C, uint32_t ldc, int acc_mode);
+
 /* Several products with the same A in ONE launch: C_list[i] = A * B_list[i], i < batch (HOST arrays of device
  * pointers; every operand N columns wide with leading dimensions ldb / ldc).  Same arithmetic and results as
  * `batch` calls of mispmm_csr_f32 (kernel 5) / mispmm_csr_uniform_f32 (uniformRowNnz > 0: rowPtrs may be NULL),
