@@ -677,3 +677,32 @@ extern "C" int mispmm_csr_panels_host(uint32_t M, uint32_t K, const uint32_t *ro
     }
     return MISPMM_OK;
 }
+
+// The pattern of A^T as a CSR, by a stable counting sort of A's entries by column: entry t of the transposed list is entry
+// perm[t] of A, so a row of A^T lists its entries by ascending row of A and repeated (row, column) pairs in storage order.
+extern "C" int mispmm_csr_transpose_host(uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs_host, const uint32_t *colIdxs_host,
+                                         uint32_t *tRowPtrs_out_host, uint32_t *tColIdxs_out_host, uint32_t *perm_out_host) {
+    if (!tRowPtrs_out_host) return fail(MISPMM_ERR_INVALID_ARG, "csr_transpose: tRowPtrs_out is null");
+    if (M != 0 && !rowPtrs_host) return fail(MISPMM_ERR_INVALID_ARG, "csr_transpose: rowPtrs is null");
+    if (nnz != 0 && (!colIdxs_host || !tColIdxs_out_host || !perm_out_host))
+        return fail(MISPMM_ERR_INVALID_ARG, "csr_transpose: colIdxs or an output is null");
+    for (uint32_t r = 0; r < M; ++r)
+        if (rowPtrs_host[r + 1] < rowPtrs_host[r]) return fail(MISPMM_ERR_INVALID_ARG, "csr_transpose: rowPtrs decrease at row %u", r);
+    if ((M == 0 && nnz != 0) || (M != 0 && (rowPtrs_host[0] != 0 || rowPtrs_host[M] != nnz)))
+        return fail(MISPMM_ERR_INVALID_ARG, "csr_transpose: rowPtrs do not span [0, nnz = %u]", nnz);
+    for (uint32_t i = 0; i < nnz; ++i)
+        if (colIdxs_host[i] >= K) return fail(MISPMM_ERR_INVALID_ARG, "csr_transpose: column index %u out of range", colIdxs_host[i]);
+    std::fill(tRowPtrs_out_host, tRowPtrs_out_host + static_cast<size_t>(K) + 1, 0u);
+    for (uint32_t i = 0; i < nnz; ++i) ++tRowPtrs_out_host[static_cast<size_t>(colIdxs_host[i]) + 1];
+    for (uint32_t c = 0; c < K; ++c) tRowPtrs_out_host[c + 1] += tRowPtrs_out_host[c];
+    // walking A in storage order keeps ties in storage order; next[c] = where column c's next entry goes
+    std::vector<uint32_t> next(tRowPtrs_out_host, tRowPtrs_out_host + K);
+    for (uint32_t r = 0; r < M; ++r) {
+        for (uint32_t i = rowPtrs_host[r]; i < rowPtrs_host[r + 1]; ++i) {
+            const uint32_t t = next[colIdxs_host[i]]++;
+            tColIdxs_out_host[t] = r;
+            perm_out_host[t] = i;
+        }
+    }
+    return MISPMM_OK;
+}

@@ -94,6 +94,9 @@ SIGNATURES = {
     "mispmm_bsr_nonzeros_f64_host": (_i, [_u32, _u32, _u32, _u32, _vp, _vp, _vp, _c.POINTER(_u32), _vp, _vp, _vp]),
     "mispmm_vendor_spmm_f64": (_i, [_vp, _i, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32,
                                     _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    "mispmm_sddmm_csr_f32": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _i]),
+    "mispmm_sddmm_csr_f64": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _i]),
+    "mispmm_csr_transpose_host": (_i, [_u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "mispmm_dense_transpose_f32": (_i, [_vp, _u32, _u32, _vp, _vp]),
     "mispmm_f32_to_bf16": (_i, [_vp, _sz, _vp, _vp]),
     "mispmm_bf16_to_f32": (_i, [_vp, _sz, _vp, _vp]),

@@ -483,6 +483,41 @@ def spmm_csr_batch(a, bs, outs=None, acc="reference", stream=None):
     return outs
 
 
+def csr_transpose(csr):
+    """(formats.CSR of A^T, perm) on the host (mispmm_csr_transpose_host): a stable counting sort of A's entries by column.
+    Entry t of A^T is entry perm[t] of A (its data is csr.data[perm]); a row of A^T lists its entries by ascending row of A,
+    a column repeated in one row of A in storage order.  perm is uint32."""
+    rp = np.ascontiguousarray(csr.row_ptrs, dtype=np.uint32)
+    ci = np.ascontiguousarray(csr.col_idxs, dtype=np.uint32)
+    nnz = int(ci.shape[0])
+    trp = np.zeros(csr.num_cols + 1, dtype=np.uint32)
+    tci, perm = np.zeros(nnz, dtype=np.uint32), np.zeros(nnz, dtype=np.uint32)
+    capi.check(capi.lib().mispmm_csr_transpose_host(csr.num_rows, csr.num_cols, nnz, rp.ctypes.data, ci.ctypes.data, trp.ctypes.data,
+                                                     tci.ctypes.data, perm.ctypes.data))
+    return formats.CSR(csr.num_cols, csr.num_rows, trp, tci, np.asarray(csr.data)[perm.astype(np.int64)]), perm
+
+
+def sddmm_csr(a, x, y, out=None, acc="reference", stream=None):
+    """out[e] = <x[row(e), :], y[col(e), :]> for every stored entry e of a (mispmm_sddmm_csr_f32 / _f64): the sampled
+    dense-dense product on A's pattern, A's values unread.  a: DeviceCSR [M x K]; x: [M, N], y: [K, N] device tensors of one
+    dtype (float32 or float64; row-major, any row stride); returns a tensor of nnz elements in A's storage order."""
+    _require_gpu(a.row_ptrs, x, y, out)
+    f64 = _check_dtype(x.dtype)
+    ld = _dense_ld_f64 if f64 else _dense_ld
+    ldx, ldy = ld(x), ld(y)
+    if x.shape[0] != a.num_rows or y.shape[0] != a.num_cols or x.shape[1] != y.shape[1]:
+        raise ValueError(f"A is {a.num_rows} x {a.num_cols}: x must be [{a.num_rows}, N] and y [{a.num_cols}, N], not "
+                         f"{tuple(x.shape)} and {tuple(y.shape)}")
+    if out is None:
+        out = torch.empty(a.nnz, dtype=x.dtype, device=x.device)
+    if out.dtype != x.dtype or out.dim() != 1 or out.shape[0] != a.nnz or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {x.dtype} tensor of {a.nnz} elements")
+    fn = capi.lib().mispmm_sddmm_csr_f64 if f64 else capi.lib().mispmm_sddmm_csr_f32
+    capi.check(fn(_stream_ptr(stream), a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs), _p(x), ldx, _p(y), ldy,
+                  x.shape[1], _p(out), capi.ACC_MODES[acc]))
+    return out
+
+
 @dataclass
 class DeviceCSRTiles:
     """A CSR with rows of one width grouped into LDS tiles (mispmm_csr_tiles_host): rows that share B rows sit in one tile of

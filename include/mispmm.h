@@ -497,6 +497,45 @@ int mispmm_vendor_spmm_f64(mispmm_stream_t stream, int format, uint32_t M, uint3
                            uint32_t N, uint32_t ldb, double *C, uint32_t ldc, double *pro_us, double *kernel_us,
                            double *epi_us);
 
+/* ---------------------------------------------------- SDDMM on a CSR pattern */
+/* Sampled dense-dense product: out[e] = sum_j X[r][j] * Y[colIdxs[e]][j] for every e in [rowPtrs[r], rowPtrs[r + 1]).
+ * X is M x N, Y is K x N, both row-major with leading dimensions ldx, ldy >= N; out holds nnz elements in A's storage
+ * order; A's values are not read.  With X = dC and Y = B this is the gradient of C = A * B with respect to A's values.
+ * New capability: the reference has no backward pass and no second dense operand.
+ * NUMERICS, with S = sum_j |x_j||y_j| and `exact` the real-number sum:
+ *   f32 REFERENCE  every product formed exactly (fp32 x fp32 fits fp64), the products summed in fp64 in a fixed order
+ *                  (a chain per lane, then a fixed tree across the lane group) and rounded to fp32 once:
+ *                  |out - exact| <= 2^-24 |exact| + N 2^-52 S.
+ *   f32 FAST       an fp32 fma chain per lane, then the same tree in fp32: |out - exact| <= g S with
+ *                  g = N 2^-24 / (1 - N 2^-24), the any-order dot-product bound.
+ *   f64 REFERENCE  product and add rounded separately (no FMA);  f64 FAST  fma.  Both: |out - exact| <= 2 N 2^-53 S.
+ *   Every mode is run-to-run identical.  Where every partial sum is exactly representable (e.g. small-integer X and Y)
+ *   all four are exact.  out[e] is NaN or +-Inf exactly where the sum of its products is; other entries are unaffected.
+ *   N == 0 writes +0 to every out[e]; nnz == 0 or M == 0 is a no-op.
+ * Any M, K, nnz, N; rows may be ragged, empty or long and may hold unsorted or repeated columns.  16-byte lanes where N, ldx,
+ * ldy are multiples of 4 (f64: 2) and X, Y are 16-byte aligned, else one element per lane.  Validates its arguments before
+ * any device work (null pointer, ldx or ldy < N: MISPMM_ERR_INVALID_ARG); an X or Y that spans 2 GiB or more is declined
+ * with MISPMM_ERR_UNSUPPORTED and nothing is launched.  Enqueues only: no allocation, no synchronisation, capturable.
+ * mispmm_last_kernel() = sddmm_csr<...>. */
+int mispmm_sddmm_csr_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs,
+                         const uint32_t *colIdxs, const float *X, uint32_t ldx, const float *Y, uint32_t ldy, uint32_t N, float *out,
+                         int acc_mode);
+int mispmm_sddmm_csr_f64(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs,
+                         const uint32_t *colIdxs, const double *X, uint32_t ldx, const double *Y, uint32_t ldy, uint32_t N, double *out,
+                         int acc_mode);
+
+/* HOST helper: the pattern of A^T (K x M) as a CSR, by a STABLE counting sort of A's entries by column.  tRowPtrs_out_host
+ * has K + 1 entries, tColIdxs_out_host and perm_out_host nnz each: entry t of the transposed list is entry perm[t] of A and
+ * tColIdxs[t] is the row of A it belongs to, so a row of A^T lists its entries by ascending row of A, ties (a column repeated
+ * in one row of A) in storage order.  A column >= K, decreasing row pointers or row pointers that do not span [0, nnz] are
+ * MISPMM_ERR_INVALID_ARG.
+ * The transposed product needs no kernel of its own: A^T * G is mispmm_csr_f32 / mispmm_csr_f64 (every kernel id, hint and
+ * entry point that takes these arrays) on (tRowPtrs, tColIdxs, vals[perm]) -- with X = dC this is the gradient of C = A * B
+ * with respect to B, and gathering vals through perm keeps it tied to A's values.  REFERENCE mode for the transposed
+ * product means the reference's CSR arithmetic on exactly these arrays: bit-identical to its CPU engine run on them. */
+int mispmm_csr_transpose_host(uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs_host, const uint32_t *colIdxs_host,
+                              uint32_t *tRowPtrs_out_host, uint32_t *tColIdxs_out_host, uint32_t *perm_out_host);
+
 /* ------------------------------------------------------------ dense helpers */
 /* dst[cols x rows] = transpose(src[rows x cols]); both dense row-major buffers.
  * Replaces the host round trip of DenseMatrix::toOrdering (dense.cu:139-191). */
