@@ -122,6 +122,7 @@ template <int G, int VEC, class Acc>
 static void launch_coo(const CooArgs &a) {
     dim3 grid(ceil_div(a.M, 256 / G), ceil_div(a.N, G * VEC));
     const uint64_t bytes = static_cast<uint64_t>(a.K) * a.ldb * 4u;
+    note_kernel("coo_k1<G%d,V%d,%s%s>", G, VEC, acc_tag<Acc>(), bytes > 0x7FFFFFFFull ? ",wide" : "");
     if (bytes > 0x7FFFFFFFull)
         hipLaunchKernelGGL((coo_k1<G, VEC, Acc, true>), grid, dim3(256), 0, a.stream, a.M, a.nnz, a.rowIdxs, a.rowPtrs,
                            a.colIdxs, a.vals, a.B, 0u, a.N, a.ldb, a.C, a.ldc);

@@ -16,6 +16,7 @@ _lib = None
 
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 _f32p = ctypes.POINTER(ctypes.c_float)
+_f64p = ctypes.POINTER(ctypes.c_double)
 
 
 def build(force=False):
@@ -48,6 +49,10 @@ def lib():
         _lib.oracle_dense_reorder_f32.restype = None
         _lib.oracle_allclose_f32.argtypes = [ctypes.c_size_t, _f32p, _f32p, ctypes.c_double, ctypes.c_double]
         _lib.oracle_allclose_f32.restype = ctypes.c_int
+        _lib.oracle_rows_fma_f32.argtypes = [ctypes.c_uint32, _u32p, _u32p, _f32p, _f32p, ctypes.c_uint32, _f32p]
+        _lib.oracle_rows_fma_f32.restype = None
+        _lib.oracle_rows_fma_f64.argtypes = [ctypes.c_uint32, _u32p, _u32p, _f64p, _f64p, ctypes.c_uint32, _f64p]
+        _lib.oracle_rows_fma_f64.restype = None
     return _lib
 
 
@@ -119,6 +124,30 @@ def spmm_bsr(num_rows, block_row_size, block_col_size, block_row_ptrs, block_col
     c = np.zeros((num_rows, n), dtype=np.float32)
     lib().oracle_spmm_bsr_f32(rp.shape[0] - 1, block_row_size, block_col_size, rpp, cip, dap, bp, n,
                               c.ctypes.data_as(_f32p))
+    return c
+
+
+def rows_fma(row_ptrs, col_idxs, vals, b):
+    """The library's own FAST contract over a row list: per output element one chain started at +0, one correctly rounded
+    fma per entry in list order.  vals and b are both float32 (fmaf) or both float64 (fma); anything else is refused, so a
+    silent conversion cannot change what is being checked."""
+    vals, b = np.asarray(vals), np.asarray(b)
+    if vals.dtype != b.dtype or vals.dtype not in (np.float32, np.float64):
+        raise TypeError(f"rows_fma takes vals and b both float32 or both float64, not {vals.dtype} and {b.dtype}")
+    if b.ndim != 2:
+        raise ValueError("b must be 2-D")
+    rp, rpp = _u32(row_ptrs)
+    ci, cip = _u32(col_idxs)
+    if ci.size and int(ci.max()) >= b.shape[0]:
+        raise ValueError("a column index is past the rows of b")
+    if int(rp[-1]) > ci.shape[0] or int(rp[-1]) > vals.shape[0]:
+        raise ValueError("row_ptrs run past col_idxs / vals")
+    fp = _f32p if vals.dtype == np.float32 else _f64p
+    va, bb = np.ascontiguousarray(vals), np.ascontiguousarray(b)
+    m, n = rp.shape[0] - 1, bb.shape[1]
+    c = np.zeros((m, n), dtype=vals.dtype)
+    fn = lib().oracle_rows_fma_f32 if vals.dtype == np.float32 else lib().oracle_rows_fma_f64
+    fn(m, rpp, cip, va.ctypes.data_as(fp), bb.ctypes.data_as(fp), n, c.ctypes.data_as(fp))
     return c
 
 

@@ -26,7 +26,16 @@
  *         spmm_bsr.cpp:17-38).  AccT is unused by the reference there.
  * Compile with -ffp-contract=off so no mul+add pair is fused: the reference's
  * default x86-64 build has no FMA instructions to contract into.
+ *
+ * The two oracle_rows_fma_* functions at the end are of another kind: they restate
+ * THIS library's own FAST contract (include/mispmm.h, enum mispmm_acc_mode; DESIGN
+ * section 2), not a reference engine -- the reference has no fused path.  One chain
+ * per output element over a row list, started at +0, one correctly rounded libm
+ * fmaf / fma per entry in list order.  tests/test_fma_chain_cpu.py pins them against
+ * exact rational arithmetic; tests/test_gpu_fast_chain.py holds the FAST kernels to
+ * their bits.
  */
+#include <math.h>
 #include <stdint.h>
 #include <stddef.h>
 #include <string.h>
@@ -197,6 +206,37 @@ int oracle_allclose_f32(size_t n, const float *c, const float *ref,
             return 0;
     }
     return 1;
+}
+
+/* The FAST contract of libmispmm over a row list (rowPtrs[M+1], colIdxs, vals) and a
+ * contiguous row-major B[K x N]:  acc = +0;  acc = fma(vals[e], B[col[e]][j], acc) for
+ * the row's entries in list order;  C[r][j] = acc.  fmaf / fma are libm's, correctly
+ * rounded whether or not the host has an FMA instruction; the multiply and the add are
+ * never written apart here, so there is nothing for a compiler to contract or split. */
+void oracle_rows_fma_f32(uint32_t numRows, const uint32_t *rowPtrs, const uint32_t *colIdxs,
+                         const float *vals, const float *bData, uint32_t bNumCols, float *cData)
+{
+    for (uint32_t r = 0; r < numRows; r++) {
+        for (uint32_t j = 0; j < bNumCols; j++) {
+            float acc = 0.0f;
+            for (uint32_t e = rowPtrs[r]; e < rowPtrs[r + 1]; e++)
+                acc = fmaf(vals[e], bData[(size_t)colIdxs[e] * bNumCols + j], acc);
+            cData[(size_t)r * bNumCols + j] = acc;
+        }
+    }
+}
+
+void oracle_rows_fma_f64(uint32_t numRows, const uint32_t *rowPtrs, const uint32_t *colIdxs,
+                         const double *vals, const double *bData, uint32_t bNumCols, double *cData)
+{
+    for (uint32_t r = 0; r < numRows; r++) {
+        for (uint32_t j = 0; j < bNumCols; j++) {
+            double acc = 0.0;
+            for (uint32_t e = rowPtrs[r]; e < rowPtrs[r + 1]; e++)
+                acc = fma(vals[e], bData[(size_t)colIdxs[e] * bNumCols + j], acc);
+            cData[(size_t)r * bNumCols + j] = acc;
+        }
+    }
 }
 
 #ifdef __cplusplus
