@@ -1,4 +1,4 @@
-"""Autograd for the CSR product: C = A @ B with A's values and B both trainable.
+"""Autograd for the CSR product and for the bf16 block-sparse (BSR) product: C = A @ B with A's values and B both trainable.
 
     a = TrainableCSR.from_host(csr)                    # patterns of A and A^T on the device, once
     w = torch.nn.Parameter(a.values)                   # A's values, in storage order
@@ -7,10 +7,19 @@
 
 Both gradients are library kernels: grad_values[e] = <grad_C[row(e), :], B[col(e), :]> is ops.sddmm_csr, grad_B = A^T grad_C
 is ops.spmm_csr on the transposed pattern with A's values gathered through the transpose's permutation, so the two stay tied
-to one set of values.  float32 and float64; no double backward."""
+to one set of values.  float32 and float64; no double backward.
+
+    a = TrainableBSR.from_host(bsr)                    # 16 x 16 or 32 x 32 blocks: block patterns of A and A^T, once
+    w = torch.nn.Parameter(a.blocks)                   # A's blocks in bfloat16, in storage order
+    c = spmm_bsr(a, w, b)                              # forward: ops.spmm_bsr_bf16 (MFMA), b bfloat16
+    c.sum().backward()                                 # w.grad: ops.sddmm_bsr_bf16; b.grad: ops.spmm_bsr_bf16 on A^T's pattern
+
+Both gradients come back in bfloat16.  Not built: COO / ELL patterns, the column-compacted block layouts (their tiles are built
+on the host from the values), a device kernel for the blocks[perm] transpose."""
 import dataclasses
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -69,3 +78,74 @@ def spmm(a, values, b, acc="reference"):
     if values.dim() != 1 or values.shape[0] != a.fwd.nnz:
         raise ValueError(f"values must hold the {a.fwd.nnz} entries of A")
     return _SpmmCsr.apply(values, b, a, acc)
+
+
+@dataclass
+class TrainableBSR:
+    fwd: ops.DeviceBSR          # A's block pattern (index arrays used; spmm_bsr() multiplies by the blocks it is given)
+    tpattern: ops.DeviceBSR     # A^T's block pattern
+    perm: torch.Tensor          # int64, device: block t of A^T is block perm[t] of A, its inner axes swapped
+    blocks: torch.Tensor        # bfloat16 [num_blocks, bS, bS]: bsr.data rounded to nearest even, for the caller to wrap as a parameter
+
+    @staticmethod
+    def from_host(bsr, device="cuda"):
+        if bsr.block_row_size != bsr.block_col_size or bsr.block_row_size not in (16, 32):
+            raise ValueError(f"the bf16 block product takes 16 x 16 or 32 x 32 blocks, not {bsr.block_row_size} x {bsr.block_col_size}")
+        t_bsr, perm = ops.bsr_transpose(bsr)
+        bs = bsr.block_row_size
+        blocks = torch.from_numpy(np.ascontiguousarray(bsr.data, dtype=np.float32).reshape(bsr.num_blocks, bs, bs)).to(torch.bfloat16)
+        return TrainableBSR(ops.DeviceBSR.from_host(bsr, device=device), ops.DeviceBSR.from_host(t_bsr, device=device),
+                            torch.from_numpy(perm.astype("int64")).to(device), blocks.to(device))
+
+
+def _bits(t):
+    return t.view(torch.int16)
+
+
+class _SpmmBsrBf16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, blocks, b, a, out_bf16):
+        ctx.a = a
+        ctx.save_for_backward(blocks, b)
+        c = ops.spmm_bsr_bf16(a.fwd, _bits(blocks.detach().contiguous()), _bits(b.detach()), out_bf16=out_bf16)
+        return c.view(torch.bfloat16) if out_bf16 else c
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_c):
+        blocks, b = ctx.saved_tensors
+        a = ctx.a
+        grad_c = grad_c.contiguous()           # e.g. C.sum().backward() hands in an expanded scalar, strides (0, 0)
+        g = ops.f32_to_bf16(grad_c) if grad_c.dtype == torch.float32 else _bits(grad_c)
+        grad_blocks = grad_b = None
+        if ctx.needs_input_grad[0]:
+            grad_blocks = ops.sddmm_bsr_bf16(a.fwd, g, _bits(b), out_bf16=True).view(torch.bfloat16)
+        if ctx.needs_input_grad[1]:
+            t_blocks = blocks.detach()[a.perm].transpose(1, 2).contiguous()
+            grad_b = ops.spmm_bsr_bf16(a.tpattern, _bits(t_blocks), g, out_bf16=True).view(torch.bfloat16)
+        return grad_blocks, grad_b, None, None
+
+
+def spmm_bsr(a, blocks, b, out_dtype=torch.float32):
+    """C = A @ B on the bf16 MFMA kernels, differentiable in `blocks` ([num_blocks, bS, bS] bfloat16, A's blocks in storage
+    order -- every element of a stored block is a parameter, its zeros included) and in `b` ([K, N] bfloat16, N a multiple of
+    4).  a: TrainableBSR; out_dtype: torch.float32 or torch.bfloat16.  The forward is ops.spmm_bsr_bf16, bit for bit.  The
+    backward makes grad_C contiguous and, where C is float32, rounds it to bfloat16 (to nearest even) first: both gradient
+    kernels take bf16 operands.  grad_blocks = ops.sddmm_bsr_bf16(A's pattern, grad_C, B), grad_B = ops.spmm_bsr_bf16 on A^T's
+    pattern with the blocks gathered through the transpose's permutation; both are accumulated in fp32, rounded once and
+    returned as bfloat16.  A gradient is computed only for the inputs that require one."""
+    ops._require_gpu(a.fwd.block_row_ptrs, blocks, b)
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16, not {out_dtype}")
+    if blocks.dtype != torch.bfloat16 or b.dtype != torch.bfloat16:
+        raise ValueError("blocks and b must be torch.bfloat16")
+    bs = a.fwd.block_row_size
+    if tuple(blocks.shape) != (a.fwd.num_blocks, bs, bs):
+        raise ValueError(f"blocks must hold the {a.fwd.num_blocks} blocks of A as [{a.fwd.num_blocks}, {bs}, {bs}], not {tuple(blocks.shape)}")
+    if b.dim() != 2 or b.shape[0] != a.fwd.num_cols:
+        raise ValueError(f"A has {a.fwd.num_cols} columns: b must be [{a.fwd.num_cols}, N], not {tuple(b.shape)}")
+    if b.shape[1] % 4 != 0:
+        raise ValueError(f"the bf16 block product takes N in multiples of 4, not {b.shape[1]}")
+    if not b.is_contiguous():
+        raise ValueError("b must be contiguous")
+    return _SpmmBsrBf16.apply(blocks, b, a, out_dtype == torch.bfloat16)

@@ -751,6 +751,50 @@ def spmm_bsr_bf16(a, blocks_bf16, b_bf16, out_bf16=False, out=None, stream=None)
     return out
 
 
+def _bf16_ld(t, what):
+    if t.dim() != 2 or t.dtype != torch.int16 or t.stride(1) != 1 and t.shape[1] > 1:
+        raise ValueError(f"{what} must be a 2-D int16 tensor of bf16 bits with unit column stride")
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+    if ld < t.shape[1]:
+        raise ValueError(f"{what} must not overlap its own rows (row stride {ld} < {t.shape[1]} columns), e.g. an expanded tensor")
+    return ld
+
+
+def sddmm_bsr_bf16(a, x_bf16, y_bf16, out_bf16=False, out=None, stream=None):
+    """out[e][i][j] = <x[R * bS + i, :], y[c * bS + j, :]> for every stored block e of a, R its block row and c its block column
+    (mispmm_sddmm_bsr_bf16): the sampled dense-dense product on A's block pattern, A's values unread.  a: DeviceBSR
+    [M x K] of 16 x 16 or 32 x 32 blocks (index arrays used); x_bf16: [M, N], y_bf16: [K, N] int16 tensors of bf16 bits
+    (row-major, any row stride); returns [num_blocks, bS, bS] in A's block order, float32, or int16 bf16 bits with out_bf16."""
+    _require_gpu(a.block_row_ptrs, x_bf16, y_bf16, out)
+    ldx, ldy = _bf16_ld(x_bf16, "x_bf16"), _bf16_ld(y_bf16, "y_bf16")
+    bs = a.block_row_size
+    if a.block_col_size != bs:
+        raise ValueError(f"blocks must be square, not {bs} x {a.block_col_size}")
+    if x_bf16.shape[0] != a.num_rows or y_bf16.shape[0] != a.num_cols or x_bf16.shape[1] != y_bf16.shape[1]:
+        raise ValueError(f"A is {a.num_rows} x {a.num_cols}: x must be [{a.num_rows}, N] and y [{a.num_cols}, N], not "
+                         f"{tuple(x_bf16.shape)} and {tuple(y_bf16.shape)}")
+    dtype = torch.int16 if out_bf16 else torch.float32
+    if out is None:
+        out = torch.empty((a.num_blocks, bs, bs), dtype=dtype, device=x_bf16.device)
+    if out.dtype != dtype or tuple(out.shape) != (a.num_blocks, bs, bs) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {dtype} tensor of shape {(a.num_blocks, bs, bs)}")
+    capi.check(capi.lib().mispmm_sddmm_bsr_bf16(_stream_ptr(stream), a.num_rows // bs, a.num_cols, bs, a.num_blocks,
+                                                _p(a.block_row_ptrs), _p(a.block_col_idxs), _p(x_bf16), ldx, _p(y_bf16), ldy,
+                                                x_bf16.shape[1], _p(out), int(bool(out_bf16))))
+    return out
+
+
+def bsr_transpose(bsr):
+    """(formats.BSR of A^T, perm) on the host: mispmm_csr_transpose_host on the block arrays, a stable counting sort of A's
+    blocks by block column.  Block t of A^T is block perm[t] of A with its two inner axes swapped; a block row of A^T lists its
+    blocks by ascending block row of A.  perm is uint32."""
+    br, bc = bsr.block_row_size, bsr.block_col_size
+    blocks = np.asarray(bsr.data).reshape(bsr.num_blocks, br, bc)
+    t, perm = csr_transpose(formats.CSR(bsr.num_rows // br, bsr.num_cols // bc, bsr.block_row_ptrs, bsr.block_col_idxs, blocks))
+    return formats.BSR(bsr.num_cols, bsr.num_rows, bsr.nnz, bc, br, t.row_ptrs, t.col_idxs,
+                       np.ascontiguousarray(t.data.transpose(0, 2, 1))), perm
+
+
 @dataclass
 class DeviceBSRC:
     """Column-compacted block rows of a 16-row BSR (mispmm_bsr_compact_bf16_host)."""

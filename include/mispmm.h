@@ -532,9 +532,46 @@ int mispmm_sddmm_csr_f64(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_
  * The transposed product needs no kernel of its own: A^T * G is mispmm_csr_f32 / mispmm_csr_f64 (every kernel id, hint and
  * entry point that takes these arrays) on (tRowPtrs, tColIdxs, vals[perm]) -- with X = dC this is the gradient of C = A * B
  * with respect to B, and gathering vals through perm keeps it tied to A's values.  REFERENCE mode for the transposed
- * product means the reference's CSR arithmetic on exactly these arrays: bit-identical to its CPU engine run on them. */
+ * product means the reference's CSR arithmetic on exactly these arrays: bit-identical to its CPU engine run on them.
+ * Called on a BSR's block arrays -- (numBlockRows, numBlockCols, numBlocks, blockRowPtrs, blockColIdxs) -- it yields the block
+ * pattern of A^T and the stable permutation of the blocks: block t of A^T is block perm[t] of A with its two inner axes
+ * swapped, and mispmm_bsr_bf16 on that pattern is the transposed block-sparse product. */
 int mispmm_csr_transpose_host(uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs_host, const uint32_t *colIdxs_host,
                               uint32_t *tRowPtrs_out_host, uint32_t *tColIdxs_out_host, uint32_t *perm_out_host);
+
+/* ---------------------------------------------------- SDDMM on a BSR pattern, bf16 */
+/* Sampled dense-dense product on a block pattern: for every stored block e of block row R, with c = blockColIdxs[e], and
+ * i, j in [0, bS):  out[e][i][j] = sum_n X[R * bS + i][n] * Y[c * bS + j][n].
+ * X is (numBlockRows * bS) x N, Y is K x N, raw bf16 bits, row-major with leading dimensions ldx, ldy >= N; out is
+ * numBlocks x bS x bS in A's block storage order (the layout of `blocks` in mispmm_bsr_bf16), fp32, or bf16 bits when
+ * out_bf16 is set: the fp32 sum rounded once, to nearest even, with the rounding of mispmm_f32_to_bf16.  A's values are not
+ * read.  With X = dC and Y = B this is the gradient of C = A * B with respect to every element of every stored block, a
+ * block's explicit zeros included (in a block-sparse layer the block is the parameter).  bS is 16 or 32, the shapes
+ * mispmm_bsr_bf16 takes (a 32 x 32 block is four 16 x 16 output tiles); any other size is MISPMM_ERR_UNSUPPORTED.
+ * ARITHMETIC: v_mfma_f32_16x16x32_bf16, fp32 accumulation, one instruction per tile and 32 columns of N, ascending.
+ * NUMERICS, with `exact` the real-number sum of the bf16 operands' products and S = sum_n |x_n||y_n|:
+ *   Run-to-run identical.
+ *   Exact on exactly representable sums: where every partial sum is exactly representable in fp32 (e.g. small-integer X
+ *   and Y with N max|x| max|y| < 2^24) the fp32 result is exact and the bf16 result its nearest-even rounding.
+ *   Other data:  fp32 out  |out - exact| <= g S,  g = N u / (1 - N u),  u = 2^-23;
+ *                bf16 out  |out - exact| <= 2^-8 |exact| + (1 + 2^-8) g S.
+ *   The product of two bf16 values is exact in fp32; g is the any-order dot-product bound for adds each accurate to one
+ *   fp32 ulp: u = 2^-23 instead of 2^-24 covers an accumulate inside the instruction that truncates instead of rounding
+ *   to nearest (its internal rounding is not specified).
+ *   out[e][i][j] is NaN or +-Inf exactly where the sum of its products is (a NaN stays a NaN in the bf16 out type too; which
+ *   NaN, sign and payload, is not specified); every other element is unaffected.
+ *   N == 0 writes +0 to every element; numBlocks == 0 or numBlockRows == 0 is a no-op.
+ * Block rows may be ragged or empty and need not list their block columns in order.  A block column index >= K / bS reads
+ * zeros through the buffer descriptor and never reads memory (the contract of mispmm_bsrc_slots_bf16).  16-byte lanes where
+ * N, ldx, ldy are multiples of 8 and X, Y are 16-byte aligned, else element by element (any N, any alignment); columns at
+ * or past N contribute +0 and the gap of a strided operand is never read.  out needs only its element's alignment.
+ * Validates its arguments before any device work: a null pointer, ldx or ldy < N, K not a multiple of bS:
+ * MISPMM_ERR_INVALID_ARG; an unsupported bS, an X or Y that spans 2 GiB or more: MISPMM_ERR_UNSUPPORTED, nothing launched.
+ * Enqueues only: no allocation, no synchronisation, capturable.  mispmm_last_kernel() = sddmm_bsr<b16|b32,wide|narrow,
+ * f32|bf16,...>.  Not built: fp32 / fp64 block SDDMM, the column-compacted and slots layouts, COO and ELL patterns. */
+int mispmm_sddmm_bsr_bf16(mispmm_stream_t stream, uint32_t numBlockRows, uint32_t K, uint32_t bS, uint32_t numBlocks,
+                          const uint32_t *blockRowPtrs, const uint32_t *blockColIdxs, const uint16_t *X, uint32_t ldx,
+                          const uint16_t *Y, uint32_t ldy, uint32_t N, void *out, int out_bf16);
 
 /* ------------------------------------------------------------ dense helpers */
 /* dst[cols x rows] = transpose(src[rows x cols]); both dense row-major buffers.
