@@ -8,11 +8,11 @@
 // in step k a lane keeps the half of its values whose entry number has bit k equal to its own lane bit k and hands the other
 // half to lane ^ (1 << k), so 8 values cross the group in 4 + 2 + 1 moves (then one per further doubling of G) instead of
 // 8 * log2(G), and lane i of the group ends up with the result of entry i of the batch: lanes 0..7 store 8 consecutive
-// elements of `out`.  The moves are DPP (quad_perm, row_ror) or ds_swizzle; lane ^ 32 goes through ds_bpermute.
+// elements of `out`.  The moves (lane_moves.hpp) are DPP (quad_perm, row_ror) or ds_swizzle; lane ^ 32 goes through ds_bpermute.
 // A batch's column keys reach the group by DPP row_newbcast: per key two moves (lane j and lane 8 + j of the 16-lane row) and
 // a select on the lane's own half, 16 moves per batch; with G >= 16 one move would do (both halves hold the same keys).
 // Fixed order throughout: run to run identical.  No LDS, no scratch.
-#include "spmm_common.hpp"
+#include "lane_moves.hpp"
 
 namespace mispmm {
 
@@ -67,26 +67,6 @@ struct SdF64Fast {
     static __device__ __forceinline__ void mac(A &acc, T x, T y) { acc = __builtin_fma(x, y, acc); }
     static __device__ __forceinline__ T finish(A acc) { return acc; }
 };
-
-// the value lane ^ MASK holds.  1, 2: quad_perm [1,0,3,2] / [2,3,0,1]; 8: row_ror:8 (a rotation by half a 16-lane row is the
-// exchange of its halves); 4, 16: ds_swizzle bit mode (and 0x1f, or 0, xor MASK; inside 32 lanes); 32: ds_bpermute.
-template <int MASK>
-__device__ __forceinline__ uint32_t lane_xor_u32(uint32_t x) {
-    const int v = static_cast<int>(x);
-    if constexpr (MASK == 1) return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true));
-    else if constexpr (MASK == 2) return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true));
-    else if constexpr (MASK == 8) return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, true));
-    else if constexpr (MASK == 4 || MASK == 16) return static_cast<uint32_t>(__builtin_amdgcn_ds_swizzle(v, (MASK << 10) | 0x1F));
-    else return static_cast<uint32_t>(__shfl_xor(v, MASK, kWave));
-}
-template <int MASK> __device__ __forceinline__ float lane_xor(float x) { return __uint_as_float(lane_xor_u32<MASK>(__float_as_uint(x))); }
-template <int MASK> __device__ __forceinline__ double lane_xor(double x) {
-    using u2 = uint32_t __attribute__((ext_vector_type(2)));
-    u2 b = __builtin_bit_cast(u2, x);
-    b[0] = lane_xor_u32<MASK>(b[0]);
-    b[1] = lane_xor_u32<MASK>(b[1]);
-    return __builtin_bit_cast(double, b);
-}
 
 // one step of the transposing butterfly: 2 * H values in, H out; the lane whose bit MASK is clear keeps the even ones
 template <int MASK, int H, class A>

@@ -1,4 +1,5 @@
-"""Autograd for the CSR product and for the bf16 block-sparse (BSR) product: C = A @ B with A's values and B both trainable.
+"""Autograd for the CSR product, for attention on a CSR pattern (SDDMM, row softmax, product) and for the bf16 block-sparse
+(BSR) product.  C = A @ B with A's values and B both trainable:
 
     a = TrainableCSR.from_host(csr)                    # patterns of A and A^T on the device, once
     w = torch.nn.Parameter(a.values)                   # A's values, in storage order
@@ -9,13 +10,23 @@ Both gradients are library kernels: grad_values[e] = <grad_C[row(e), :], B[col(e
 is ops.spmm_csr on the transposed pattern with A's values gathered through the transpose's permutation, so the two stay tied
 to one set of values.  float32 and float64; no double backward.
 
+The same pattern carries an attention layer (GAT, graph transformers, masked attention on a fixed pattern):
+
+    scores = sddmm(a, q * scale, k)                    # ops.sddmm_csr; backward: two products, with A's and A^T's pattern
+    p = edge_softmax(a, scores)                        # ops.softmax_csr over every row's entries; backward: ops.softmax_csr_bwd
+    out = spmm(a, p, v)                                # the product above
+    out = sparse_attention(a, q, k, v)                 # the three lines as one call
+
+Every step and every gradient is a library kernel; a mask is a -Inf score.  The block-sparse product:
+
     a = TrainableBSR.from_host(bsr)                    # 16 x 16 or 32 x 32 blocks: block patterns of A and A^T, once
     w = torch.nn.Parameter(a.blocks)                   # A's blocks in bfloat16, in storage order
     c = spmm_bsr(a, w, b)                              # forward: ops.spmm_bsr_bf16 (MFMA), b bfloat16
     c.sum().backward()                                 # w.grad: ops.sddmm_bsr_bf16; b.grad: ops.spmm_bsr_bf16 on A^T's pattern
 
-Both gradients come back in bfloat16.  Not built: COO / ELL patterns, the column-compacted block layouts (their tiles are built
-on the host from the values), a device kernel for the blocks[perm] transpose."""
+Both gradients come back in bfloat16.  Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, a fused
+SDDMM + softmax, the column-compacted block layouts (their tiles are built on the host from the values), a device kernel for
+the blocks[perm] transpose."""
 import dataclasses
 from dataclasses import dataclass
 
@@ -78,6 +89,97 @@ def spmm(a, values, b, acc="reference"):
     if values.dim() != 1 or values.shape[0] != a.fwd.nnz:
         raise ValueError(f"values must hold the {a.fwd.nnz} entries of A")
     return _SpmmCsr.apply(values, b, a, acc)
+
+
+class _SddmmCsr(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, a, acc):
+        ctx.a, ctx.acc = a, acc
+        ctx.save_for_backward(x, y)
+        return ops.sddmm_csr(a.fwd, x.detach(), y.detach(), acc=acc)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        a = ctx.a
+        g = g.contiguous()
+        grad_x = grad_y = None
+        if ctx.needs_input_grad[0]:       # dX[r] = sum over row r of g[e] Y[col(e)]:  (A's pattern, values g) @ Y
+            grad_x = ops.spmm_csr(dataclasses.replace(a.fwd, data=g), y, acc=ctx.acc)
+        if ctx.needs_input_grad[1]:       # dY[c] = sum over column c of g[e] X[row(e)]:  (A^T's pattern, values g[perm]) @ X
+            grad_y = ops.spmm_csr(dataclasses.replace(a.tpattern, data=g[a.perm]), x, acc=ctx.acc)
+        return grad_x, grad_y, None, None
+
+
+def _check_operand(t, rows, dtype, what):
+    if t.dtype != dtype:
+        raise ValueError(f"{what} must be {dtype}, like the matrix")
+    if t.dim() != 2 or t.shape[0] != rows:
+        raise ValueError(f"{what} must be [{rows}, N], not {tuple(t.shape)}")
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError(f"{what} must have unit column stride")
+
+
+def sddmm(a, x, y, acc="reference"):
+    """scores[e] = <x[row(e), :], y[col(e), :]> for every stored entry e of A, differentiable in x ([M, N]) and y ([K, N]).
+    a: TrainableCSR (its values are not read); the forward is ops.sddmm_csr, each gradient one ops.spmm_csr with the incoming
+    gradient as A's values -- on A's pattern for x, on A^T's for y -- and is computed only if its input requires one."""
+    ops._require_gpu(a.fwd.row_ptrs, x, y)
+    dtype = a.fwd.data.dtype
+    _check_operand(x, a.fwd.num_rows, dtype, "x")
+    _check_operand(y, a.fwd.num_cols, dtype, "y")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"x and y must have the same number of columns, not {x.shape[1]} and {y.shape[1]}")
+    return _SddmmCsr.apply(x, y, a, acc)
+
+
+class _EdgeSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, a, acc):
+        p = ops.softmax_csr(a.fwd, scores.detach().contiguous(), acc=acc)
+        ctx.a, ctx.acc = a, acc
+        ctx.save_for_backward(p)
+        return p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dp):
+        (p,) = ctx.saved_tensors
+        return ops.softmax_csr_bwd(ctx.a.fwd, p, dp.contiguous(), acc=ctx.acc), None, None
+
+
+def edge_softmax(a, scores, acc="reference"):
+    """The softmax of every row of A over its stored entries (ops.softmax_csr), differentiable in `scores` (a.fwd.nnz
+    elements in storage order).  a: TrainableCSR.  The result is saved; the backward is ops.softmax_csr_bwd on it."""
+    ops._require_gpu(a.fwd.row_ptrs, scores)
+    if scores.dtype != a.fwd.data.dtype:
+        raise ValueError(f"scores must be {a.fwd.data.dtype}, like the matrix")
+    if scores.dim() != 1 or scores.shape[0] != a.fwd.nnz:
+        raise ValueError(f"scores must hold the {a.fwd.nnz} entries of A")
+    return _EdgeSoftmax.apply(scores, a, acc)
+
+
+def sparse_attention(a, q, k, v, scale=None, acc="reference"):
+    """Attention on A's pattern: row r attends to the columns A stores in row r.
+
+        scores = sddmm(a, q * scale, k)        # [nnz]   <q_r, k_c> for every stored (r, c)
+        p = edge_softmax(a, scores)            # [nnz]   softmax over each row's entries
+        out = spmm(a, p, v)                    # [M, Dv] sum over the row of p[e] v[col(e)]
+
+    a: TrainableCSR [M x K] (its values are not read); q: [M, D], k: [K, D], v: [K, Dv] device tensors of a's dtype (float32
+    or float64), unit column stride.  scale defaults to D ** -0.5 and is applied to q by a torch multiply.  Differentiable in
+    q, k and v; a row of A without entries gives a zero row."""
+    ops._require_gpu(a.fwd.row_ptrs, q, k, v)
+    dtype = a.fwd.data.dtype
+    _check_operand(q, a.fwd.num_rows, dtype, "q")
+    _check_operand(k, a.fwd.num_cols, dtype, "k")
+    _check_operand(v, a.fwd.num_cols, dtype, "v")
+    if q.shape[1] != k.shape[1]:
+        raise ValueError(f"q and k must have the same number of columns, not {q.shape[1]} and {k.shape[1]}")
+    if scale is None:
+        scale = q.shape[1] ** -0.5
+    return spmm(a, edge_softmax(a, sddmm(a, q * scale, k, acc=acc), acc=acc), v, acc=acc)
 
 
 @dataclass

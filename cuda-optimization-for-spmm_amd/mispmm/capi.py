@@ -97,6 +97,10 @@ SIGNATURES = {
     "mispmm_sddmm_csr_f32": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _i]),
     "mispmm_sddmm_csr_f64": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _i]),
     "mispmm_csr_transpose_host": (_i, [_u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "mispmm_softmax_csr_f32": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _i]),
+    "mispmm_softmax_csr_f64": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _i]),
+    "mispmm_softmax_csr_bwd_f32": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _i]),
+    "mispmm_softmax_csr_bwd_f64": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _i]),
     "mispmm_sddmm_bsr_bf16": (_i, [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _i]),
     "mispmm_dense_transpose_f32": (_i, [_vp, _u32, _u32, _vp, _vp]),
     "mispmm_f32_to_bf16": (_i, [_vp, _sz, _vp, _vp]),

@@ -518,6 +518,49 @@ def sddmm_csr(a, x, y, out=None, acc="reference", stream=None):
     return out
 
 
+def _entries(a, t, what):
+    """t as an array over A's entries: a contiguous 1-D float32 / float64 device tensor of nnz elements."""
+    if t.dim() != 1 or t.shape[0] != a.nnz or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous 1-D tensor of the {a.nnz} entries of A, not {tuple(t.shape)} with strides {tuple(t.stride())}")
+
+
+def softmax_csr(a, scores, out=None, acc="reference", stream=None):
+    """out[e] = exp(scores[e] - m_r) / sum over row r of exp(scores[e'] - m_r), m_r the row's largest score
+    (mispmm_softmax_csr_f32 / _f64): the softmax of every row of a's pattern over its stored entries.  a: DeviceCSR, of which
+    only row_ptrs, num_rows and nnz are used; scores: nnz elements in A's storage order, float32 or float64.  A -Inf score is
+    a masked entry (+0); a row with a NaN, a +Inf or nothing but -Inf is NaN throughout.  out may be scores itself."""
+    _require_gpu(a.row_ptrs, scores, out)
+    f64 = _check_dtype(scores.dtype)
+    _entries(a, scores, "scores")
+    if out is None:
+        out = torch.empty_like(scores)
+    if out.dtype != scores.dtype:
+        raise ValueError(f"out must be {scores.dtype}, like scores")
+    _entries(a, out, "out")
+    fn = capi.lib().mispmm_softmax_csr_f64 if f64 else capi.lib().mispmm_softmax_csr_f32
+    capi.check(fn(_stream_ptr(stream), a.num_rows, a.nnz, _p(a.row_ptrs), _p(scores), _p(out), capi.ACC_MODES[acc]))
+    return out
+
+
+def softmax_csr_bwd(a, p, dp, out=None, acc="reference", stream=None):
+    """ds[e] = p[e] * (dp[e] - sum over row r of p[e'] * dp[e']) (mispmm_softmax_csr_bwd_f32 / _f64): the gradient of
+    softmax_csr with respect to the scores, given its result p and the gradient dp of that result.  out may be dp itself."""
+    _require_gpu(a.row_ptrs, p, dp, out)
+    f64 = _check_dtype(p.dtype)
+    if dp.dtype != p.dtype:
+        raise ValueError(f"dp must be {p.dtype}, like p")
+    _entries(a, p, "p")
+    _entries(a, dp, "dp")
+    if out is None:
+        out = torch.empty_like(dp)
+    if out.dtype != p.dtype:
+        raise ValueError(f"out must be {p.dtype}, like p")
+    _entries(a, out, "out")
+    fn = capi.lib().mispmm_softmax_csr_bwd_f64 if f64 else capi.lib().mispmm_softmax_csr_bwd_f32
+    capi.check(fn(_stream_ptr(stream), a.num_rows, a.nnz, _p(a.row_ptrs), _p(p), _p(dp), _p(out), capi.ACC_MODES[acc]))
+    return out
+
+
 @dataclass
 class DeviceCSRTiles:
     """A CSR with rows of one width grouped into LDS tiles (mispmm_csr_tiles_host): rows that share B rows sit in one tile of

@@ -539,6 +539,63 @@ int mispmm_sddmm_csr_f64(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_
 int mispmm_csr_transpose_host(uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs_host, const uint32_t *colIdxs_host,
                               uint32_t *tRowPtrs_out_host, uint32_t *tColIdxs_out_host, uint32_t *perm_out_host);
 
+/* ---------------------------------------------------- Row softmax on a CSR pattern */
+/* The middle step of attention on a fixed pattern (scores = SDDMM, P = softmax per row, out = P * V), and its backward.
+ * scores, out, p, dp, ds are device arrays of nnz elements in A's storage order; row r owns the elements
+ * [rowPtrs[r], rowPtrs[r + 1]).  Column indices and A's values are not read.  New capability: the reference has neither.
+ *   forward   out[e] = exp(s[e] - m_r) / sum_{e' in row r} exp(s[e'] - m_r),   m_r the largest score of row r
+ *   backward  ds[e]  = p[e] * (dp[e] - sum_{e' in row r} p[e'] * dp[e']),      p the forward's result
+ * SPECIAL VALUES, as torch.softmax on the row's entries: a -Inf score is a masked entry and gives exactly +0 where the row
+ * has a finite score; a row that holds a NaN, a +Inf, or nothing but -Inf is NaN in every entry; no other row is affected.
+ * A row of one finite entry is exactly 1.  An empty row writes nothing.  The backward of an all-zero dp is all +0.
+ * IN PLACE: out may be the same array as scores, and ds the same as dp (any other overlap is undefined).
+ * NUMERICS OF THE FORWARD.  L = the row's length, T = max |s[e] - m_r| over the row's finite scores, `exact` the
+ * real-number value, tiny = the smallest subnormal of the out type:
+ *   f32 REFERENCE  scores widened to fp64; difference, exp (the device library's double exp, 1 ulp), sum in a fixed order
+ *                  and division in fp64; rounded to fp32 once:
+ *                  |out - exact| <= 2^-24 exact + (L + 2 T + 8) 2^-52 exact + 2 tiny.
+ *   f64            fp64 throughout, the same arithmetic in both modes:
+ *                  |out - exact| <= (L + 2 T + 8) 2^-52 exact + 2 tiny.
+ *   f32 FAST       fp32 throughout, exp as v_exp_f32 of fl(t * log2 e):
+ *                  |out - exact| <= (L + 8 T + 16) 2^-24 exact + 2^-126.
+ *   Derivation (u = 2^-53, resp. 2^-24 for FAST; every operation correctly rounded, both exps accurate to 1 ulp = 2 u):
+ *   the difference t = s - m_r carries a relative error u, which the exp turns into |t| u (FAST: the rounded constant and the
+ *   rounded product add 2 |t| u more); so a term E_e is off by at most (T + 2) u (FAST (3 T + 2) u) relative, in the
+ *   numerator and, as a weighted mean, in the sum; the sum adds at most (L - 1) u whatever its order, the division u:
+ *   (L + 2 T + 4) u in all (FAST (L + 6 T + 4) u).  The stated bounds hold (2 L + 4 T + 16) u, resp. (L + 8 T + 16) u: the
+ *   margin covers second-order terms.  2 tiny: a result that lands in the subnormal range is rounded to a multiple of tiny;
+ *   FAST's 2^-126: v_exp_f32 and the fp32 division may flush a subnormal result to zero.
+ *   In REFERENCE and f64 a row whose scores are all equal gives the correctly rounded 1 / L (exp(0) = 1 and the sum of L
+ *   ones are exact; f32: the fp64 quotient rounded to fp32).  The quotients of a row sum to 1 within L u of the out type's
+ *   mode (2^-24, f64 2^-53): a term's own error is in numerator and denominator alike.
+ * NUMERICS OF THE BACKWARD, with S = sum over the row of |p||dp|:
+ *   f32 REFERENCE  products (exact) and sums in fp64, rounded once:
+ *                  |ds - exact| <= 2^-24 |exact| + (L + 4) 2^-52 p[e] (|dp[e]| + S) + tiny.
+ *   f64            REFERENCE product and add rounded separately, FAST fma:
+ *                  |ds - exact| <= (L + 4) 2^-52 p[e] (|dp[e]| + S) + (L + 2) tiny.
+ *   f32 FAST       an fp32 fma chain:  |ds - exact| <= g p[e] (|dp[e]| + S) + (L + 2) 2^-126,
+ *                  g = (L + 4) 2^-24 / (1 - (L + 4) 2^-24).
+ *   The last term of each is the underflow term, as in the forward: the relative terms hold for results in the normal
+ *   range only.  A forward result p[e] may itself be subnormal (scores 100 apart in fp32), and then ds[e] ~ p[e] lands on
+ *   the subnormal grid, where rounding is off by up to tiny / 2 whatever the magnitude -- no fp32 value is closer.  f32
+ *   REFERENCE underflows only there (an fp64 product of fp32 values cannot); in f64 and FAST each of the row's L products
+ *   and the two final operations may, FAST possibly flushing to zero (2^-126 instead of tiny / 2).
+ * Every mode is run-to-run identical: a lane sums its entries in ascending order, the lanes of a row meet in a fixed tree.
+ * Any M, any nnz, any row length; rows may be ragged or empty.  acc_mode other than MISPMM_ACC_REFERENCE / _FAST or a null
+ * pointer is MISPMM_ERR_INVALID_ARG, found before any device work; nnz == 0 or M == 0 is a no-op.  The kernels address
+ * through 64-bit pointers: no array size is declined.  Enqueues only: one launch, no allocation, no synchronisation,
+ * capturable.  mispmm_last_kernel() = softmax_csr<...> / softmax_csr_bwd<...> (arithmetic, G lanes per row, R entries per
+ * lane held in registers).  Not built: a split form that deals one very long row to several waves, a fused
+ * SDDMM + softmax, bf16, COO / ELL patterns. */
+int mispmm_softmax_csr_f32(mispmm_stream_t stream, uint32_t M, uint32_t nnz, const uint32_t *rowPtrs, const float *scores,
+                           float *out, int acc_mode);
+int mispmm_softmax_csr_f64(mispmm_stream_t stream, uint32_t M, uint32_t nnz, const uint32_t *rowPtrs, const double *scores,
+                           double *out, int acc_mode);
+int mispmm_softmax_csr_bwd_f32(mispmm_stream_t stream, uint32_t M, uint32_t nnz, const uint32_t *rowPtrs, const float *p,
+                               const float *dp, float *ds, int acc_mode);
+int mispmm_softmax_csr_bwd_f64(mispmm_stream_t stream, uint32_t M, uint32_t nnz, const uint32_t *rowPtrs, const double *p,
+                               const double *dp, double *ds, int acc_mode);
+
 /* ---------------------------------------------------- SDDMM on a BSR pattern, bf16 */
 /* Sampled dense-dense product on a block pattern: for every stored block e of block row R, with c = blockColIdxs[e], and
  * i, j in [0, bS):  out[e][i][j] = sum_n X[R * bS + i][n] * Y[c * bS + j][n].
