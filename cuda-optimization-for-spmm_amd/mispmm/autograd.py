@@ -251,3 +251,119 @@ def spmm_bsr(a, blocks, b, out_dtype=torch.float32):
     if not b.is_contiguous():
         raise ValueError("b must be contiguous")
     return _SpmmBsrBf16.apply(blocks, b, a, out_dtype == torch.bfloat16)
+
+
+# ---- attention on a block pattern in bf16: SDDMM (fp32 scores), row softmax (bf16 P), product
+def _check_block_array(a, t, what):
+    bs = a.fwd.block_row_size
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what} must be torch.float32")
+    if tuple(t.shape) != (a.fwd.num_blocks, bs, bs):
+        raise ValueError(f"{what} must hold the {a.fwd.num_blocks} blocks of A as [{a.fwd.num_blocks}, {bs}, {bs}], not {tuple(t.shape)}")
+
+
+def _check_out_dtype(out_dtype):
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16, not {out_dtype}")
+    return out_dtype == torch.bfloat16
+
+
+class _BlockSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, a, scale, mask, out_bf16):
+        p = ops.softmax_bsr(a.fwd, scores.detach().contiguous(), scale=scale, mask=mask, out_bf16=out_bf16)
+        ctx.a, ctx.scale = a, scale
+        ctx.save_for_backward(p)
+        return p.view(torch.bfloat16) if out_bf16 else p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dp):
+        (p,) = ctx.saved_tensors
+        return ops.softmax_bsr_bwd(ctx.a.fwd, p, dp.float().contiguous(), scale=ctx.scale), None, None, None, None
+
+
+def block_softmax(a, scores, scale=1.0, mask=None, out_dtype=torch.float32):
+    """The softmax of every matrix row of A over the elements of its stored blocks (ops.softmax_bsr), of scale * scores + mask,
+    differentiable in `scores` ([num_blocks, bS, bS] float32 in A's block order); `mask` (float32, the same shape, -Inf = masked)
+    is a constant.  a: TrainableBSR; out_dtype: torch.float32 or torch.bfloat16.  The result is saved in the out type; the
+    backward is ops.softmax_bsr_bwd on it, with the incoming gradient widened to float32 and a float32 result."""
+    ops._require_gpu(a.fwd.block_row_ptrs, scores, mask)
+    out_bf16 = _check_out_dtype(out_dtype)
+    _check_block_array(a, scores, "scores")
+    if mask is not None:
+        _check_block_array(a, mask, "mask")
+        mask = mask.detach().contiguous()
+    return _BlockSoftmax.apply(scores, a, float(scale), mask, out_bf16)
+
+
+class _BlockSparseAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, a, scale, mask, out_bf16):
+        q, k, v = q.detach(), k.detach(), v.detach()
+        s = ops.sddmm_bsr_bf16(a.fwd, _bits(q), _bits(k))
+        p = ops.softmax_bsr(a.fwd, s, scale=scale, mask=mask, out_bf16=True)
+        out = ops.spmm_bsr_bf16(a.fwd, p, _bits(v), out_bf16=out_bf16)
+        ctx.a, ctx.scale = a, scale
+        ctx.save_for_backward(q, k, v, p)
+        return out.view(torch.bfloat16) if out_bf16 else out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v, p = ctx.saved_tensors
+        a = ctx.a
+        grad_out = grad_out.contiguous()           # e.g. out.sum().backward() hands in an expanded scalar, strides (0, 0)
+        g = ops.f32_to_bf16(grad_out) if grad_out.dtype == torch.float32 else _bits(grad_out)
+        transposed = lambda blocks: blocks[a.perm].transpose(1, 2).contiguous()   # noqa: E731  A's blocks as A^T's
+        grad_q = grad_k = grad_v = None
+        if ctx.needs_input_grad[2]:
+            grad_v = ops.spmm_bsr_bf16(a.tpattern, transposed(p), g, out_bf16=True).view(torch.bfloat16)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            dp = ops.sddmm_bsr_bf16(a.fwd, g, _bits(v))
+            ds = ops.softmax_bsr_bwd(a.fwd, p, dp, scale=ctx.scale, out_bf16=True)
+            if ctx.needs_input_grad[0]:
+                grad_q = ops.spmm_bsr_bf16(a.fwd, ds, _bits(k), out_bf16=True).view(torch.bfloat16)
+            if ctx.needs_input_grad[1]:
+                grad_k = ops.spmm_bsr_bf16(a.tpattern, transposed(ds), _bits(q), out_bf16=True).view(torch.bfloat16)
+        return grad_q, grad_k, grad_v, None, None, None, None
+
+
+def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.float32):
+    """Attention on A's block pattern in bf16: matrix row r attends to the columns of the blocks A stores in r's block row.
+
+        S = ops.sddmm_bsr_bf16(q, k)                               # fp32 [num_blocks, bS, bS]: <q_r, k_c>, fp32 accumulation
+        P = ops.softmax_bsr(S, scale, mask, out_bf16=True)         # softmax of scale * S + mask per matrix row, bf16
+        out = ops.spmm_bsr_bf16(P, v)                              # [M, Dv], fp32 accumulation
+
+    a: TrainableBSR [M x K] (its values are not read); q: [M, D], k: [K, D], v: [K, Dv], bfloat16 and contiguous, D and Dv
+    multiples of 4.  scale defaults to D ** -0.5 and is applied inside the softmax kernel, to the fp32 scores: q is not rounded
+    again.  mask: float32 [num_blocks, bS, bS], added to the scaled scores, -Inf = masked (e.g. above the diagonal of the
+    diagonal blocks for a block-causal pattern); a constant.  out_dtype: torch.float32 or torch.bfloat16.
+    One autograd.Function, so that no bf16 intermediate is widened on the way.  Roundings: the scores stay fp32; P is the fp32
+    softmax rounded to bf16 once (to nearest even) and is what the product multiplies by and what the backward reads; out is
+    the fp32 sum, rounded once if bfloat16.  Backward: grad_out is made contiguous and, where float32, rounded to bf16 first
+    (every kernel here takes bf16 operands); dV = ops.spmm_bsr_bf16 on A^T's pattern with P's blocks gathered through the
+    transpose's permutation; dP = ops.sddmm_bsr_bf16(grad_out, v) in fp32; dS = ops.softmax_bsr_bwd(P, dP, scale) rounded to
+    bf16 once; dQ = ops.spmm_bsr_bf16(dS, k); dK = ops.spmm_bsr_bf16 on A^T's pattern with dS's blocks gathered likewise and q.
+    The three gradients are fp32 sums rounded once and returned as bfloat16.  Each gradient, and each kernel behind it, runs
+    only if its input requires it.  A block row of A without blocks gives zero rows."""
+    ops._require_gpu(a.fwd.block_row_ptrs, q, k, v, mask)
+    out_bf16 = _check_out_dtype(out_dtype)
+    for t, rows, what in ((q, a.fwd.num_rows, "q"), (k, a.fwd.num_cols, "k"), (v, a.fwd.num_cols, "v")):
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"{what} must be torch.bfloat16")
+        if t.dim() != 2 or t.shape[0] != rows:
+            raise ValueError(f"{what} must be [{rows}, N], not {tuple(t.shape)}")
+        if t.shape[1] % 4 != 0:
+            raise ValueError(f"the bf16 block product takes widths in multiples of 4: {what} has {t.shape[1]} columns")
+        if not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+    if q.shape[1] != k.shape[1]:
+        raise ValueError(f"q and k must have the same number of columns, not {q.shape[1]} and {k.shape[1]}")
+    if mask is not None:
+        _check_block_array(a, mask, "mask")
+        mask = mask.detach().contiguous()
+    if scale is None:
+        scale = q.shape[1] ** -0.5
+    return _BlockSparseAttention.apply(q, k, v, a, float(scale), mask, out_bf16)

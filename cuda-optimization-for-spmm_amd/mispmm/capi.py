@@ -102,6 +102,8 @@ SIGNATURES = {
     "mispmm_softmax_csr_bwd_f32": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _i]),
     "mispmm_softmax_csr_bwd_f64": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _i]),
     "mispmm_sddmm_bsr_bf16": (_i, [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _i]),
+    "mispmm_softmax_bsr_f32": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _c.c_float, _vp, _i]),
+    "mispmm_softmax_bsr_bwd_f32": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _i, _vp, _c.c_float, _vp, _i]),
     "mispmm_dense_transpose_f32": (_i, [_vp, _u32, _u32, _vp, _vp]),
     "mispmm_f32_to_bf16": (_i, [_vp, _sz, _vp, _vp]),
     "mispmm_bf16_to_f32": (_i, [_vp, _sz, _vp, _vp]),

@@ -827,6 +827,59 @@ def sddmm_bsr_bf16(a, x_bf16, y_bf16, out_bf16=False, out=None, stream=None):
     return out
 
 
+def _block_array(a, t, dtypes, what):
+    """t as an array over A's block elements: a contiguous [num_blocks, bS, bS] device tensor of one of `dtypes`."""
+    bs = a.block_row_size
+    if t.dtype not in dtypes or tuple(t.shape) != (a.num_blocks, bs, bs) or not t.is_contiguous():
+        names = " or ".join(str(d) for d in dtypes)
+        raise ValueError(f"{what} must be a contiguous {names} tensor of shape {(a.num_blocks, bs, bs)}, not {t.dtype} {tuple(t.shape)} "
+                         f"with strides {tuple(t.stride())}")
+
+
+def _square_blocks(a):
+    if a.block_col_size != a.block_row_size:
+        raise ValueError(f"blocks must be square, not {a.block_row_size} x {a.block_col_size}")
+
+
+def softmax_bsr(a, scores, scale=1.0, mask=None, out_bf16=False, out=None, stream=None):
+    """out = softmax over every matrix row of z = scale * scores + mask (one fp32 fma; without a mask the product), a row
+    being element row i of all blocks of a block row (mispmm_softmax_bsr_f32).  a: DeviceBSR of 16 x 16 or 32 x 32 blocks, of
+    which only block_row_ptrs and the sizes are used; scores and mask: float32 [num_blocks, bS, bS] in A's block order, as
+    sddmm_bsr_bf16 writes them; a -Inf in mask is a masked position (+0).  Returns [num_blocks, bS, bS] float32, or int16 bf16
+    bits with out_bf16 -- the blocks spmm_bsr_bf16 takes.  out must not overlap scores or mask."""
+    _require_gpu(a.block_row_ptrs, scores, mask, out)
+    _square_blocks(a)
+    _block_array(a, scores, (torch.float32,), "scores")
+    if mask is not None:
+        _block_array(a, mask, (torch.float32,), "mask")
+    dtype = torch.int16 if out_bf16 else torch.float32
+    if out is None:
+        out = torch.empty(scores.shape, dtype=dtype, device=scores.device)
+    _block_array(a, out, (dtype,), "out")
+    bs = a.block_row_size
+    capi.check(capi.lib().mispmm_softmax_bsr_f32(_stream_ptr(stream), a.num_rows // bs, bs, a.num_blocks, _p(a.block_row_ptrs),
+                                                 _p(scores), _p(mask), float(scale), _p(out), int(bool(out_bf16))))
+    return out
+
+
+def softmax_bsr_bwd(a, p, dp, scale=1.0, out_bf16=False, out=None, stream=None):
+    """ds = scale * p * (dp - sum over the matrix row of p * dp) (mispmm_softmax_bsr_bwd_f32): the gradient of softmax_bsr
+    with respect to the scores, given its result p (float32, or int16 bf16 bits: the dtype says which) and the float32
+    gradient dp of that result.  Returns float32, or int16 bf16 bits with out_bf16.  out must not overlap p or dp."""
+    _require_gpu(a.block_row_ptrs, p, dp, out)
+    _square_blocks(a)
+    _block_array(a, p, (torch.float32, torch.int16), "p")
+    _block_array(a, dp, (torch.float32,), "dp")
+    dtype = torch.int16 if out_bf16 else torch.float32
+    if out is None:
+        out = torch.empty(dp.shape, dtype=dtype, device=dp.device)
+    _block_array(a, out, (dtype,), "out")
+    bs = a.block_row_size
+    capi.check(capi.lib().mispmm_softmax_bsr_bwd_f32(_stream_ptr(stream), a.num_rows // bs, bs, a.num_blocks, _p(a.block_row_ptrs),
+                                                     _p(p), int(p.dtype == torch.int16), _p(dp), float(scale), _p(out), int(bool(out_bf16))))
+    return out
+
+
 def bsr_transpose(bsr):
     """(formats.BSR of A^T, perm) on the host: mispmm_csr_transpose_host on the block arrays, a stable counting sort of A's
     blocks by block column.  Block t of A^T is block perm[t] of A with its two inner axes swapped; a block row of A^T lists its

@@ -630,6 +630,68 @@ int mispmm_sddmm_bsr_bf16(mispmm_stream_t stream, uint32_t numBlockRows, uint32_
                           const uint32_t *blockRowPtrs, const uint32_t *blockColIdxs, const uint16_t *X, uint32_t ldx,
                           const uint16_t *Y, uint32_t ldy, uint32_t N, void *out, int out_bf16);
 
+/* ---------------------------------------------------- Row softmax on a BSR pattern */
+/* The middle step of attention on a block pattern in bf16 -- scores = mispmm_sddmm_bsr_bf16 (fp32 out), P = this softmax
+ * (bf16 out), out = mispmm_bsr_bf16 with P as the blocks -- and its backward.  A is numBlockRows block rows of square
+ * bS x bS blocks, bS 16 or 32, blockRowPtrs as in mispmm_bsr_bf16.  scores, mask, out, p, dp, ds are device arrays of
+ * numBlocks x bS x bS elements in A's block storage order (what mispmm_sddmm_bsr_bf16 writes and mispmm_bsr_bf16 reads).
+ * Matrix row R * bS + i owns element row i of every block e in [blockRowPtrs[R], blockRowPtrs[R + 1]); its length is
+ * L = bS * (blocks of block row R).  Block column indices and A's values are not read.  New capability: the reference has
+ * neither.
+ *   forward   z[e][i][j]   = fl32(scale * s[e][i][j] + mask[e][i][j])   one fp32 fma; mask == NULL: the fp32 product scale * s
+ *             out[e][i][j] = exp(z - m) / sum_row exp(z - m),           m the largest z of the matrix row
+ *   backward  ds[e][i][j]  = scale * p * (dp - sum_row p * dp),         p the forward's result
+ * scores, mask, dp are fp32.  out (out_bf16), p (p_bf16) and ds (ds_bf16) are fp32, or raw bf16 bits when the flag is
+ * set: a bf16 result is the fp32 result rounded once, to nearest even, with the rounding of mispmm_f32_to_bf16; a bf16 p
+ * is widened exactly.  scale is applied here and not to Q: multiplying a bf16 Q by D^-0.5 would round Q a second time.
+ * mask is an additive array (block-causal diagonals, biases); a -Inf entry is a masked position.
+ * ARITHMETIC: one mode, fp32 throughout; exp is v_exp_f32 of fl(t * log2 e), as mispmm_softmax_csr_f32 in FAST mode; the
+ * backward's row sum is an fp32 fma chain, then dp - sum, the product with p and the product with scale, each rounded.
+ * SPECIAL VALUES, as torch.softmax over the L values z of a matrix row: -Inf beside a finite z gives exactly +0; a row
+ * that holds a NaN, a +Inf, or nothing but -Inf is NaN in every element of that matrix row and no other row is affected,
+ * the other rows of the same blocks included; a NaN stays a NaN in bf16.  A row with one finite z is exactly 1.  An empty
+ * block row writes nothing.  The backward of an all-zero dp is all +0.
+ * NOT IN PLACE: out must not overlap scores or mask, and ds must not overlap p or dp (the arrays differ in element size
+ * in the flagship use, and a long block row is read more than once).
+ * NUMERICS OF THE FORWARD.  `exact` is the real-number softmax of the fp32 values z as defined above (the fma that forms z
+ * is part of the definition, not of the error); T = max |z - m| over the row's finite z.
+ *   fp32 out   |out - exact| <= (L + 8 T + 16) 2^-24 exact + 2^-126
+ *   bf16 out   |out - exact| <= 2^-8 exact + (1 + 2^-8) ((L + 8 T + 16) 2^-24 exact + 2^-126) + 2^-126
+ *   The fp32 bound is the FAST bound of mispmm_softmax_csr_f32 and its derivation carries over word for word (the
+ *   difference z - m, the rounded constant and product ahead of v_exp_f32, the exp to 1 ulp: (3 T + 2) u per term; the sum
+ *   (L - 1) u in ANY order -- here: a lane's ascending chain, a butterfly over the 4 or 8 lanes of a row, then
+ *   ((w0 + w1) + w2) + w3 over the workgroup's waves; the division u; 2^-126: v_exp_f32 and the division may flush a
+ *   subnormal result).  bf16: rounding r to bf16 is off by at most 2^-9 r <= 2^-8 r / 2 in the normal range, and
+ *   r <= exact + (fp32 bound), which gives the first two terms with room; a result below 2^-126 lands on bf16's subnormal
+ *   grid (spacing 2^-133) or is flushed to zero: the last 2^-126.
+ *   fp32 row sums are within L 2^-24 of 1: a term's own error is in numerator and denominator alike.
+ *   Equal z throughout a row gives exp2(0) = 1 per term, the exact sum L and the correctly rounded fp32 quotient 1 / L.
+ * NUMERICS OF THE BACKWARD.  `exact` is the real-number result on the given p, dp and scale; S = sum_row |p||dp|.
+ *   fp32 out   |ds - exact| <= scale g p (|dp| + S) + (L + 3) 2^-126 max(1, scale),   g = (L + 5) u / (1 - (L + 5) u), u = 2^-24
+ *   bf16 out   |ds - exact| <= 2^-8 |exact| + (1 + 2^-8) (the fp32 bound) + 2^-126
+ *   Derivation: the row sum of L products by fma in any order is off by at most g_L S (g_n = n u / (1 - n u)); dp - sum
+ *   adds u (|dp| + S), and the products with p and with scale one rounding each: (L + 3) u to first order, against L + 2 for
+ *   mispmm_softmax_csr_bwd_f32 in FAST mode, which has no scale.  Stated with L + 5, as that one is with L + 4: the margin
+ *   covers second-order terms.  Underflow: each of the L fmas and the two operations before the scaling may flush
+ *   (2^-126 each, carried through the factor scale), the scaling itself once more: (L + 3) 2^-126 max(1, scale).
+ * Run-to-run identical: the order of every sum is fixed by the block row's length.  No atomics.
+ * One workgroup per block row.  A block row of up to C blocks -- C = 32 at bS = 16, 16 at bS = 32 -- is read once and held
+ * in registers; a longer one is walked three times (backward: twice), to the same bits.  mispmm_last_kernel() =
+ * softmax_bsr<b16|b32,f32|bf16,held|walk,C<n>,mask|nomask> and softmax_bsr_bwd<b16|b32,f32|bf16,held|walk,C<n>,p_f32|p_bf16>
+ * (the second field is the out type).  `held`: numBlocks <= C, so every block row of the launch is held; `walk`: the
+ * launch walks the block rows of more than C blocks (and still holds the others) -- the host does not read blockRowPtrs.
+ * Validates before any device work: a scale that is not finite or not > 0 is MISPMM_ERR_INVALID_ARG; a bS other than 16 or
+ * 32 is MISPMM_ERR_UNSUPPORTED; numBlocks == 0 or numBlockRows == 0 is then a no-op; a null pointer other than mask is
+ * MISPMM_ERR_INVALID_ARG.  Element offsets are 64-bit: no array size is declined.  The arrays need only their element's
+ * alignment.  Enqueues only: one launch, no allocation, no synchronisation, capturable.  Not built: a fused
+ * SDDMM + softmax + product, fp32 / fp64 block scores in other layouts, the column-compacted and slots layouts. */
+int mispmm_softmax_bsr_f32(mispmm_stream_t stream, uint32_t numBlockRows, uint32_t bS, uint32_t numBlocks,
+                           const uint32_t *blockRowPtrs, const float *scores, const float *mask /* may be NULL */, float scale,
+                           void *out, int out_bf16);
+int mispmm_softmax_bsr_bwd_f32(mispmm_stream_t stream, uint32_t numBlockRows, uint32_t bS, uint32_t numBlocks,
+                               const uint32_t *blockRowPtrs, const void *p, int p_bf16, const float *dp, float scale, void *ds,
+                               int ds_bf16);
+
 /* ------------------------------------------------------------ dense helpers */
 /* dst[cols x rows] = transpose(src[rows x cols]); both dense row-major buffers.
  * Replaces the host round trip of DenseMatrix::toOrdering (dense.cu:139-191). */
