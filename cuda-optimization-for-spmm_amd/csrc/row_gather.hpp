@@ -439,6 +439,170 @@ __global__ __launch_bounds__(BLOCK, ROLL ? (UMAX > 8 ? 3 : MISPMM_X_WAVES) : 1) 
     );
 }
 
+// ---- the straight-line body: rows of ONE known length (uniform CSR, ELL), 9..14 slots ---------------------------------
+// What the rolling body computes for such a row, with everything around the products taken out of the wave's path
+// ("the straight-line wave"):
+//   * no scalar load between the sums and the store, none in front of the first B read: the 13 preloaded dwords are exactly
+//     what a wave needs up to its first B read (ldb * 4 and the byte bounds come ready-made from the host), and what is
+//     left (C, its byte bound, ldc, the row map; the batched launch's b[bz] / c[bz] pair) is one aligned block behind
+//     them, fetched at the top of the wave and first used after the (col, val) reads have been issued;
+//   * (col, val) through buffer descriptors with a 32-bit offset: no 64-bit address arithmetic, a row past M is a dropped
+//     load, not an exec region (needs M * width * 4 < 2 GiB: row_line_fits);
+//   * no loop, no vote, no second arm: SLOTS issues and SLOTS sums in the rolling order (8 in flight), then the store --
+//     masked by a dropped offset, not by a branch.
+// Products, their order and their rounding are those of the rolling body: bit-identical results in both modes.
+struct alignas(16) LineTail {  // 16-byte aligned behind the preloaded dwords: one s_load_dwordx4 (+ x2 for the row map)
+    float *C;
+    uint32_t c_bytes, ldc4;  // ldc4 = ldc * 4
+    const uint32_t *rowMap;
+    uint64_t reserved;
+};
+struct LineBatchPair {
+    const float *b;
+    float *c;
+};
+template <bool BATCHED> struct LineBatch {};
+template <> struct alignas(16) LineBatch<true> {
+    LineBatchPair p[kMaxBatch];  // operand bz: one 16-byte read at a wave-uniform offset
+};
+
+template <int G, class Acc, bool PADDED, int SLOTS, bool BATCHED, bool MAPPED>
+__global__ __launch_bounds__(128, MISPMM_X_WAVES) void row_line_kernel(
+    // 13 dwords, preloaded into SGPRs at wave launch
+    const uint32_t *__restrict__ colIdxs, const float *__restrict__ vals, const float *__restrict__ B_one, uint32_t b_bytes,
+    uint32_t ldb4, uint32_t width, uint32_t M, uint32_t rb_chunk, uint32_t log2p, uint32_t cols_per_part,
+    // fetched by the wave
+    LineTail tail, LineBatch<BATCHED> batch
+#ifdef MISPMM_STAMPS
+    , uint32_t stamp_launch
+#endif
+    ) {
+#ifdef MISPMM_STAMPS
+    unsigned long long stamp[5];
+    stamp[0] = wall_clock64();
+#endif
+    constexpr int VEC = 4, BLOCK = 128, GROUPS = BLOCK / G, U = 8, E = (SLOTS + G - 1) / G;
+    static_assert((G == 8 || G == 16) && SLOTS > U && SLOTS < 16, "rows of 9..14 slots");
+    using vec_t = f32x4;
+    // everything that is not preloaded is requested HERE, in front of the (col, val) reads, and waited for at its first use
+    // (the barrier keeps the scheduler from moving the scalar loads down to where their values are needed)
+    const float *__restrict__ B = B_one;
+    float *__restrict__ C = tail.C;
+    const uint32_t c_bytes = tail.c_bytes, ldc4 = tail.ldc4;
+    const uint32_t *__restrict__ rowMap = tail.rowMap;
+    if constexpr (BATCHED) {
+        const LineBatchPair pr = batch.p[blockIdx.z];
+        B = pr.b;
+        C = pr.c;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const uint32_t lane = threadIdx.x % G;
+    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
+    const uint32_t p = xcd & ((1u << log2p) - 1u), q = xcd >> log2p;
+    const uint32_t row = (p * rb_chunk + slot) * GROUPS + threadIdx.x / G;
+    const bool row_ok = row < M;
+    // the column parts tile N exactly ((q + 1) * cols_per_part <= N: xcd_tiling), so a lane is inside N iff it is inside its part
+    const uint32_t part_col = blockIdx.y * (G * VEC) + lane * VEC;
+    const bool col_ok = part_col < cols_per_part;
+    const uint32_t col0 = q * cols_per_part + part_col;
+
+    // (col, val): entry min(idx, width - 1) of the row -- always a read inside the row -- or nothing at all for a row past M
+    const uint32_t a_bytes = M * width * 4u;  // < 2 GiB (row_line_fits)
+    const rsrc_t colrs = make_rsrc(colIdxs, a_bytes), valrs = make_rsrc(vals, a_bytes);
+    const uint32_t row_pos = row * width;
+    uint32_t raw_col[E], raw_val[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const uint32_t idx = static_cast<uint32_t>(e * G) + lane;
+        const uint32_t pos4 = row_ok ? (row_pos + min(idx, width - 1u)) * 4u : kDropLoad;
+        raw_col[e] = __builtin_amdgcn_raw_buffer_load_b32(colrs, pos4, 0, 0);
+        raw_val[e] = __builtin_amdgcn_raw_buffer_load_b32(valrs, pos4, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);  // both reads leave before anything that is not needed for them is computed
+    uint32_t out_row = row;
+    if constexpr (MAPPED) out_row = __builtin_amdgcn_raw_buffer_load_b32(make_rsrc(rowMap, M * 4u), row_ok ? row * 4u : kDropLoad, 0, 0);
+    const rsrc_t brs = make_rsrc(B, b_bytes);
+    const rsrc_t crs = make_rsrc(C, c_bytes);
+    const uint32_t lane_off = col_ok ? col0 * 4u : kDropLoad;  // lanes past the column part never fetch
+    // where this lane's four results go; a row past M or a lane past the column part stores out of range, i.e. nowhere
+    // (out_row enters at the store itself: the row map may arrive as late as that)
+    const uint32_t store_col4 = col0 * 4u;
+    const bool store_ok = row_ok && col_ok;
+#ifdef MISPMM_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stamp[1] = wall_clock64();
+#endif
+    // entries past the row's end, rows past M and ELL padding become a dropped load with a zero coefficient, once per lane:
+    // the offset is exactly kDropLoad, which stays out of range after the lane's column offset is added (in a column-masked
+    // lane the sum wraps to 0: a harmless in-range read whose lane never stores).  Branch-free, and every loaded value is used
+    // whatever the predicate says (see row_stream.hpp: a select on the predicate lets hipcc sink the load behind a branch).
+    uint32_t my_off[E], my_val[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const uint32_t idx = static_cast<uint32_t>(e * G) + lane;
+        bool drop = !row_ok || idx >= width;
+        if constexpr (PADDED) drop = drop || raw_col[e] == 0xFFFFFFFFu;
+        const uint32_t keep = drop ? 0u : 0xFFFFFFFFu;
+        my_off[e] = ((raw_col[e] * ldb4) & keep) | (drop ? kDropLoad : 0u);
+        my_val[e] = raw_val[e] & keep;
+    }
+    typename Acc::T acc[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 0;
+    vec_t bv[U];
+    float av[U];
+    auto issue_one = [&](auto slot_tag, vec_t &b, float &a) {
+        constexpr int S = decltype(slot_tag)::value;
+        const uint32_t off = group_bcast<G, S % G>(my_off[S / G]);
+        a = __builtin_bit_cast(float, group_bcast<G, S % G>(my_val[S / G]));
+        b = buffer_load_vec<VEC, MISPMM_B_LOAD_AUX>(brs, off + lane_off, 0);
+    };
+    auto consume_one = [&](const vec_t &b, float a) {
+        if constexpr (std::is_same_v<Acc, AccRefWide>) {
+            Acc::mac4(acc, a, b[0], b[1], b[2], b[3]);
+        } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) Acc::mac(acc[v], a, b[v]);
+        }
+    };
+    static_for<0, U>([&](auto s) { issue_one(s, bv[decltype(s)::value], av[decltype(s)::value]); });
+    __builtin_amdgcn_sched_barrier(0);
+    static_for<0, SLOTS>([&](auto s) {
+        constexpr int S = decltype(s)::value;
+        consume_one(bv[S % U], av[S % U]);
+        if constexpr (S + U < SLOTS) {
+            // the refill may not be hoisted above the sums it waits for (see the rolling body)
+            asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]) : : "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            issue_one(std::integral_constant<int, S + U>{}, bv[S % U], av[S % U]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    });
+#ifdef MISPMM_STAMPS
+    asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]) : : "memory");
+    stamp[2] = wall_clock64();
+#endif
+    vec_t out;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) out[v] = Acc::finish(acc[v]);
+    buffer_store_vec_c<VEC>(crs, store_ok ? out_row * ldc4 + store_col4 : kDropLoad, out);
+#ifdef MISPMM_STAMPS
+    stamp[3] = wall_clock64();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stamp[4] = wall_clock64();
+    if (mispmm_stamp_buf && (threadIdx.x & 63) == 0) {
+        const uint32_t wpb = blockDim.x / 64;
+        const size_t waves_per_launch = static_cast<size_t>(gridDim.x) * gridDim.y * wpb;
+        unsigned long long *o = mispmm_stamp_buf + (stamp_launch * waves_per_launch +
+            (static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x) * wpb + (threadIdx.x >> 6)) * 8;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) o[i] = stamp[i];
+        o[5] = static_cast<unsigned long long>(__builtin_amdgcn_s_getreg((31 << 11) | 4));
+        o[6] = static_cast<unsigned long long>(__builtin_amdgcn_s_getreg((31 << 11) | 20));
+    }
+#endif
+}
+
 // ---- host side -------------------------------------------------------------------------------
 template <class Rows> constexpr const char *rows_tag() {
     if constexpr (std::is_same_v<Rows, CsrRows>) return "csr";
@@ -604,6 +768,53 @@ void launch_row_gather_b(const RowGatherArgs &a, const Rows &rows, const XcdTili
 #undef MISPMM_STAMP_ARG
 }
 
+// Which launches the straight-line body takes: its (col, val) reads go through 32-bit buffer offsets whose bit 31 marks a
+// dropped load, and its store is a buffer store -- both arrays of A and all of C stay below 2 GiB.  Everything else keeps
+// the rolling body.
+inline bool row_line_fits(uint32_t M, uint32_t width, uint32_t ldc) {
+    return static_cast<uint64_t>(M) * width * 4u <= 0x7FFFFFFFull && static_cast<uint64_t>(M) * ldc * 4u <= 0x7FFFFFFFull;
+}
+
+// rows of one length, 9..14 slots: the straight-line body (row_line_kernel).  Returns false where it does not apply.
+template <int G, class Acc, class Rows, int SLOTS>
+bool launch_row_line(const RowGatherArgs &a, const Rows &rows, const XcdTiling &t) {
+    static const bool line_on = knob_int("MISPMM_LINE", 1) != 0;  // MISPMM_LINE=0: the rolling body (measurement aid)
+    if (!line_on || !t.sc1 || !row_line_fits(a.M, rows.width, a.ldc)) return false;
+    constexpr int VEC = 4, BLOCK = 128;
+    const uint32_t cols_per_part = a.N / t.q;
+    const uint32_t rb_chunk = ceil_div(ceil_div(a.M, BLOCK / G), 1u << t.log2p);
+    dim3 grid(8u * rb_chunk, ceil_div(cols_per_part, G * VEC));
+    const uint32_t b_bytes = static_cast<uint32_t>(static_cast<uint64_t>(a.K) * a.ldb * 4u);
+    LineTail tail{a.C, static_cast<uint32_t>(static_cast<uint64_t>(a.M) * a.ldc * 4u), a.ldc * 4u, a.rowMap, 0};
+    note_kernel("row_gather<G%d,V%d,%s,%s,B%d,U%d,%s,S%d> xcd %ux%u%s%s", G, VEC, acc_tag<Acc>(), rows_tag<Rows>(), BLOCK, 8, "line", SLOTS,
+                1u << t.log2p, t.q, a.batch ? " batched" : "", a.rowMap ? " plan-order" : "");
+#ifdef MISPMM_STAMPS
+    static uint32_t stamp_counter = 0;
+    const uint32_t stamp_launch = stamp_counter++ % kStampLaunches;
+#define MISPMM_STAMP_ARG , stamp_launch
+#else
+#define MISPMM_STAMP_ARG
+#endif
+#define MISPMM_LINE_LAUNCH(BATCHED, MAPPED, B_PTR, BATCH_ARG)                                                                          \
+    hipLaunchKernelGGL((row_line_kernel<G, Acc, Rows::kPadded, SLOTS, BATCHED, MAPPED>), grid, dim3(BLOCK), 0, a.stream, a.colIdxs, a.vals, \
+                       B_PTR, b_bytes, a.ldb * 4u, rows.width, a.M, rb_chunk, t.log2p, cols_per_part, tail, BATCH_ARG MISPMM_STAMP_ARG)
+    if (a.batch > 0) {  // one launch for the whole batch (batch <= kMaxBatch: the callers split longer lists)
+        LineBatch<true> arg;
+        for (uint32_t i = 0; i < kMaxBatch; ++i) arg.p[i] = LineBatchPair{a.B_list[i < a.batch ? i : 0], a.C_list[i < a.batch ? i : 0]};
+        tail.C = nullptr;
+        grid.z = a.batch;
+        if (a.rowMap) MISPMM_LINE_LAUNCH(true, true, nullptr, arg);
+        else MISPMM_LINE_LAUNCH(true, false, nullptr, arg);
+    } else if (a.rowMap) {
+        MISPMM_LINE_LAUNCH(false, true, a.B, LineBatch<false>{});
+    } else {
+        MISPMM_LINE_LAUNCH(false, false, a.B, LineBatch<false>{});
+    }
+#undef MISPMM_LINE_LAUNCH
+#undef MISPMM_STAMP_ARG
+    return true;
+}
+
 template <int G, int VEC, class Acc, class Rows>
 void launch_row_gather(const RowGatherArgs &a, const Rows &rows, const XcdTiling &t) {
     // 128-thread workgroups: with 256 threads a CU holds 3.08 workgroups on the headline, so some CUs
@@ -623,8 +834,15 @@ void launch_row_gather(const RowGatherArgs &a, const Rows &rows, const XcdTiling
         // (MISPMM_SLOTS=0 keeps the generic 16)
         static const bool slots = knob_int("MISPMM_SLOTS", 1) != 0;
         if (roll && slots) {
-            if (rows.width > 8 && rows.width <= 10) return launch_row_gather_b<G, VEC, Acc, Rows, 128, 8, true, 10>(a, rows, t);
-            if (rows.width > 10 && rows.width <= 12) return launch_row_gather_b<G, VEC, Acc, Rows, 128, 8, true, 12>(a, rows, t);
+            // the straight-line body where it applies (row_line_fits), else the rolling body with as many slots
+            if (rows.width > 8 && rows.width <= 10) {
+                if (launch_row_line<G, Acc, Rows, 10>(a, rows, t)) return;
+                return launch_row_gather_b<G, VEC, Acc, Rows, 128, 8, true, 10>(a, rows, t);
+            }
+            if (rows.width > 10 && rows.width <= 12) {
+                if (launch_row_line<G, Acc, Rows, 12>(a, rows, t)) return;
+                return launch_row_gather_b<G, VEC, Acc, Rows, 128, 8, true, 12>(a, rows, t);
+            }
             // (4 / 5 / 6 / 7 reads in flight instead of 8 on the headline: 3.85 / 3.74 / 3.72 / 3.67 us against 3.60-3.73)
 #ifdef MISPMM_TUNING
             if constexpr (G == 16 && std::is_same_v<Rows, UniformRows>) {  // workgroup size of the headline's kernel (measurement aid)
@@ -632,7 +850,10 @@ void launch_row_gather(const RowGatherArgs &a, const Rows &rows, const XcdTiling
                 if (rows.width > 12 && rows.width <= 14 && block == 256) return launch_row_gather_b<G, VEC, Acc, Rows, 256, 8, true, 14>(a, rows, t);
             }
 #endif
-            if (rows.width > 12 && rows.width <= 14) return launch_row_gather_b<G, VEC, Acc, Rows, 128, 8, true, 14>(a, rows, t);
+            if (rows.width > 12 && rows.width <= 14) {
+                if (launch_row_line<G, Acc, Rows, 14>(a, rows, t)) return;
+                return launch_row_gather_b<G, VEC, Acc, Rows, 128, 8, true, 14>(a, rows, t);
+            }
         }
     }
     // (A kernel specialised on the bet of the general entry point -- CsrRows with exactly nnz / M slots per super-chunk, i.e. the

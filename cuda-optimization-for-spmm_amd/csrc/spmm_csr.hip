@@ -625,6 +625,11 @@ extern "C" int mispmm_debug_split_stats(unsigned long long out[2]) {
 }
 #endif
 
+#ifdef MISPMM_TUNING
+// measurement build only: the host-side rule that admits a launch to the straight-line body (row_line_fits) -- 1 / 0
+extern "C" int mispmm_debug_row_line_fits(uint32_t M, uint32_t width, uint32_t ldc) { return row_line_fits(M, width, ldc) ? 1 : 0; }
+#endif
+
 extern "C" int mispmm_csr_uniform_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t rowNnz,
                                       const uint32_t *colIdxs, const float *vals, const float *B, uint32_t N, uint32_t ldb,
                                       float *C, uint32_t ldc, int acc_mode) {
