@@ -74,8 +74,9 @@ def test_sddmm_is_exact_on_small_integers(name, n, dt):
         assert np.array_equal(got.astype(np.float64), exact), f"{name} N={n} {dt} {acc}: {int((got != exact).sum())} entries differ"
 
 
-# every kernel instance the dispatcher can pick that the widths above leave out: 4 register chunks of 16-byte lanes (f32
-# N = 1024), the chunk loop with 16-byte lanes (N = 1028 / 516) and with narrow ones (N = 257), 4 narrow chunks (N = 255)
+# the chunked bodies the widths above leave out: 4 register chunks of 16-byte lanes (f32 N = 1024), the chunk loop with
+# 16-byte lanes (N = 1028 / 516) and with narrow ones (N = 257), 4 narrow chunks (N = 255).  Not every instance the dispatcher
+# can pick: tests/test_gpu_census.py runs each of the 56 by its tag (table sddmm_csr of tests/_census.py).
 @pytest.mark.parametrize("dt,n,tag", [("f32", 1024, "V4,C4"), ("f32", 1028, "V4,C0"), ("f32", 257, "V1,C0"), ("f32", 255, "V1,C4"),
                                       ("f64", 516, "V2,C0"), ("f64", 257, "V1,C0"), ("f64", 129, "V1,C4")])
 def test_sddmm_wide_rows_take_the_chunked_bodies(dt, n, tag):
