@@ -904,15 +904,10 @@ void launch_row_gather_auto(const RowGatherArgs &a, const Rows &rows, int vec) {
                   : (vec == 4 && cpp % 64 == 0) ? 16
                   : (vec == 4 && cpp % 32 == 0) ? 8
                                                 : pick_group(cpp, vec);
-#define MISPMM_RG_CASE(GG, VV)                                     \
-    if (g == GG && vec == VV) {                                    \
-        launch_row_gather<GG, VV, Acc, Rows>(a, rows, t);          \
-        return;                                                    \
-    }
-    MISPMM_RG_CASE(8, 4) MISPMM_RG_CASE(16, 4) MISPMM_RG_CASE(32, 4) MISPMM_RG_CASE(64, 4)
-    MISPMM_RG_CASE(8, 2) MISPMM_RG_CASE(16, 2) MISPMM_RG_CASE(32, 2) MISPMM_RG_CASE(64, 2)
-    MISPMM_RG_CASE(8, 1) MISPMM_RG_CASE(16, 1) MISPMM_RG_CASE(32, 1) MISPMM_RG_CASE(64, 1)
-#undef MISPMM_RG_CASE
+    // a forced group outside the list launches nothing
+    try_const<4, 2, 1>(vec, [&](auto v) {
+        try_const<8, 16, 32, 64>(g, [&](auto gg) { launch_row_gather<decltype(gg)::value, decltype(v)::value, Acc, Rows>(a, rows, t); });
+    });
 }
 
 }  // namespace mispmm

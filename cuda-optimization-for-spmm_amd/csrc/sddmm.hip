@@ -203,15 +203,10 @@ void launch_sddmm(const SdArgs<typename P::T> &a) {
 
 template <class P, int VEC>
 void launch_sddmm_shape(const SdArgs<typename P::T> &a) {
-    const int g = pick_group(a.N, VEC);
-    if (g == 8) return launch_sddmm<P, 8, VEC, 1>(a);
-    if (g == 16) return launch_sddmm<P, 16, VEC, 1>(a);
-    if (g == 32) return launch_sddmm<P, 32, VEC, 1>(a);
+    if (try_const<8, 16, 32>(pick_group(a.N, VEC), [&](auto g) { launch_sddmm<P, decltype(g)::value, VEC, 1>(a); })) return;
+    // a whole wave per row: 1, 2 or 4 chunks of 64 lanes held in registers, 0 = a loop over any number
     const uint32_t chunks = ceil_div(a.N, static_cast<uint32_t>(kWave * VEC));
-    if (chunks <= 1) return launch_sddmm<P, 64, VEC, 1>(a);
-    if (chunks == 2) return launch_sddmm<P, 64, VEC, 2>(a);
-    if (chunks <= 4) return launch_sddmm<P, 64, VEC, 4>(a);
-    launch_sddmm<P, 64, VEC, 0>(a);
+    with_const<1, 2, 4, 0>(chunks <= 1 ? 1 : chunks == 2 ? 2 : chunks <= 4 ? 4 : 0, [&](auto c) { launch_sddmm<P, 64, VEC, decltype(c)::value>(a); });
 }
 
 template <class PRef, class PFast>
@@ -220,8 +215,7 @@ int sddmm_csr(const char *name, mispmm_stream_t stream, uint32_t M, uint32_t K, 
               typename PRef::T *out, int acc_mode) {
     using T = typename PRef::T;
     constexpr int WIDE = 16 / sizeof(T);  // elements of a 16-byte lane
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "%s: unknown accumulate mode %d", name, acc_mode);
+    if (int s = check_acc_mode(name, acc_mode)) return s;
     if (M == 0 || nnz == 0) return MISPMM_OK;
     if (!rowPtrs || !colIdxs || !out) return fail(MISPMM_ERR_INVALID_ARG, "%s: rowPtrs, colIdxs or out is null", name);
     if (ldx < N || ldy < N)
@@ -233,17 +227,13 @@ int sddmm_csr(const char *name, mispmm_stream_t stream, uint32_t M, uint32_t K, 
     }
     if (!X || !Y) return fail(MISPMM_ERR_INVALID_ARG, "%s: X or Y is null", name);
     // a raw buffer descriptor spans less than 2 GiB and bit 31 of an offset marks a dropped load
-    if (static_cast<uint64_t>(M) * ldx * sizeof(T) > 0x7FFFFFFFull || static_cast<uint64_t>(K) * ldy * sizeof(T) > 0x7FFFFFFFull)
+    if (!fits_buffer(M, ldx, sizeof(T)) || !fits_buffer(K, ldy, sizeof(T)))
         return fail(MISPMM_ERR_UNSUPPORTED, "%s: X or Y spans 2 GiB or more (M=%u ldx=%u K=%u ldy=%u)", name, M, ldx, K, ldy);
     const SdArgs<T> a{as_stream(stream), M, K, N, rowPtrs, colIdxs, X, ldx, Y, ldy, out};
     const bool wide = N % WIDE == 0 && ldx % WIDE == 0 && ldy % WIDE == 0 && aligned16(X) && aligned16(Y);
-    if (acc_mode == MISPMM_ACC_REFERENCE) {
-        if (wide) launch_sddmm_shape<PRef, WIDE>(a);
-        else launch_sddmm_shape<PRef, 1>(a);
-    } else {
-        if (wide) launch_sddmm_shape<PFast, WIDE>(a);
-        else launch_sddmm_shape<PFast, 1>(a);
-    }
+    with_acc<PRef, PFast>(acc_mode, [&](auto acc) {
+        with_const<WIDE, 1>(wide ? WIDE : 1, [&](auto v) { launch_sddmm_shape<typename decltype(acc)::type, decltype(v)::value>(a); });
+    });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }

@@ -213,17 +213,6 @@ void launch_sddmm_bsr_width(const SbArgs &a) {
     }
 }
 
-template <int BS>
-void launch_sddmm_bsr_body(const SbArgs &a, bool wide, bool out_bf16) {
-    if (wide) {
-        if (out_bf16) launch_sddmm_bsr_width<BS, true, true>(a);
-        else launch_sddmm_bsr_width<BS, true, false>(a);
-    } else {
-        if (out_bf16) launch_sddmm_bsr_width<BS, false, true>(a);
-        else launch_sddmm_bsr_width<BS, false, false>(a);
-    }
-}
-
 }  // namespace
 
 }  // namespace mispmm
@@ -252,8 +241,11 @@ extern "C" int mispmm_sddmm_bsr_bf16(mispmm_stream_t stream, uint32_t numBlockRo
                     static_cast<unsigned long long>(numBlockRows) * bS, ldx, K, ldy);
     const SbArgs a{as_stream(stream), numBlockRows, K / bS, N, blockRowPtrs, blockColIdxs, X, ldx, Y, ldy, out};
     const bool wide = N % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && aligned16(X) && aligned16(Y);
-    if (bS == 16) launch_sddmm_bsr_body<16>(a, wide, out_bf16 != 0);
-    else launch_sddmm_bsr_body<32>(a, wide, out_bf16 != 0);
+    with_const<16, 32>(static_cast<int>(bS), [&](auto bs) {
+        with_flag(wide, [&](auto w) {
+            with_flag(out_bf16 != 0, [&](auto o) { launch_sddmm_bsr_width<decltype(bs)::value, decltype(w)::value, decltype(o)::value>(a); });
+        });
+    });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }

@@ -312,36 +312,12 @@ void launch_fwd(hipStream_t stream, uint32_t Mb, uint32_t numBlocks, const uint3
                        scale, out);
 }
 
-template <int BS>
-void launch_fwd_body(hipStream_t stream, uint32_t Mb, uint32_t numBlocks, const uint32_t *blockRowPtrs, const float *scores,
-                     const float *mask, float scale, void *out, bool out_bf16) {
-    if (mask) {
-        if (out_bf16) launch_fwd<BS, true, true>(stream, Mb, numBlocks, blockRowPtrs, scores, mask, scale, out);
-        else launch_fwd<BS, true, false>(stream, Mb, numBlocks, blockRowPtrs, scores, mask, scale, out);
-    } else {
-        if (out_bf16) launch_fwd<BS, false, true>(stream, Mb, numBlocks, blockRowPtrs, scores, mask, scale, out);
-        else launch_fwd<BS, false, false>(stream, Mb, numBlocks, blockRowPtrs, scores, mask, scale, out);
-    }
-}
-
 template <int BS, bool P_BF16, bool DS_BF16>
 void launch_bwd(hipStream_t stream, uint32_t Mb, uint32_t numBlocks, const uint32_t *blockRowPtrs, const void *p, const float *dp,
                 float scale, void *ds) {
     note_kernel("softmax_bsr_bwd<b%d,%s,%s,C%d,p_%s>", BS, DS_BF16 ? "bf16" : "f32", path_tag<BS>(numBlocks), kHeld<BS>, P_BF16 ? "bf16" : "f32");
     hipLaunchKernelGGL((softmax_bsr_bwd_kernel<BS, P_BF16, DS_BF16>), dim3(Mb), dim3(64 * kSbmWaves), 0, stream, Mb, blockRowPtrs, p, dp, scale,
                        ds);
-}
-
-template <int BS>
-void launch_bwd_body(hipStream_t stream, uint32_t Mb, uint32_t numBlocks, const uint32_t *blockRowPtrs, const void *p, bool p_bf16,
-                     const float *dp, float scale, void *ds, bool ds_bf16) {
-    if (p_bf16) {
-        if (ds_bf16) launch_bwd<BS, true, true>(stream, Mb, numBlocks, blockRowPtrs, p, dp, scale, ds);
-        else launch_bwd<BS, true, false>(stream, Mb, numBlocks, blockRowPtrs, p, dp, scale, ds);
-    } else {
-        if (ds_bf16) launch_bwd<BS, false, true>(stream, Mb, numBlocks, blockRowPtrs, p, dp, scale, ds);
-        else launch_bwd<BS, false, false>(stream, Mb, numBlocks, blockRowPtrs, p, dp, scale, ds);
-    }
 }
 
 // what both entry points check, before any device work
@@ -364,8 +340,14 @@ extern "C" int mispmm_softmax_bsr_f32(mispmm_stream_t stream, uint32_t numBlockR
     if (const int st = check_common("softmax_bsr_f32", bS, scale)) return st;
     if (numBlockRows == 0 || numBlocks == 0) return MISPMM_OK;
     if (!blockRowPtrs || !scores || !out) return fail(MISPMM_ERR_INVALID_ARG, "softmax_bsr_f32: blockRowPtrs, scores or out is null");
-    if (bS == 16) launch_fwd_body<16>(as_stream(stream), numBlockRows, numBlocks, blockRowPtrs, scores, mask, scale, out, out_bf16 != 0);
-    else launch_fwd_body<32>(as_stream(stream), numBlockRows, numBlocks, blockRowPtrs, scores, mask, scale, out, out_bf16 != 0);
+    with_const<16, 32>(static_cast<int>(bS), [&](auto bs) {
+        with_flag(mask != nullptr, [&](auto m) {
+            with_flag(out_bf16 != 0, [&](auto o) {
+                launch_fwd<decltype(bs)::value, decltype(m)::value, decltype(o)::value>(as_stream(stream), numBlockRows, numBlocks, blockRowPtrs,
+                                                                                        scores, mask, scale, out);
+            });
+        });
+    });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
@@ -376,8 +358,14 @@ extern "C" int mispmm_softmax_bsr_bwd_f32(mispmm_stream_t stream, uint32_t numBl
     if (const int st = check_common("softmax_bsr_bwd_f32", bS, scale)) return st;
     if (numBlockRows == 0 || numBlocks == 0) return MISPMM_OK;
     if (!blockRowPtrs || !p || !dp || !ds) return fail(MISPMM_ERR_INVALID_ARG, "softmax_bsr_bwd_f32: blockRowPtrs, p, dp or ds is null");
-    if (bS == 16) launch_bwd_body<16>(as_stream(stream), numBlockRows, numBlocks, blockRowPtrs, p, p_bf16 != 0, dp, scale, ds, ds_bf16 != 0);
-    else launch_bwd_body<32>(as_stream(stream), numBlockRows, numBlocks, blockRowPtrs, p, p_bf16 != 0, dp, scale, ds, ds_bf16 != 0);
+    with_const<16, 32>(static_cast<int>(bS), [&](auto bs) {
+        with_flag(p_bf16 != 0, [&](auto pb) {
+            with_flag(ds_bf16 != 0, [&](auto db) {
+                launch_bwd<decltype(bs)::value, decltype(pb)::value, decltype(db)::value>(as_stream(stream), numBlockRows, numBlocks, blockRowPtrs, p,
+                                                                                          dp, scale, ds);
+            });
+        });
+    });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }

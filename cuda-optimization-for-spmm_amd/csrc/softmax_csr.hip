@@ -245,30 +245,20 @@ void launch_softmax(hipStream_t stream, uint32_t M, const uint32_t *rowPtrs, con
     }
 }
 
-template <class P>
-void launch_softmax_group(hipStream_t stream, uint32_t M, uint32_t nnz, const uint32_t *rowPtrs, const typename P::T *a,
-                          const typename P::T *b, typename P::T *out, bool bwd) {
-    switch (sm_pick_group(M, nnz)) {
-    case 4: return launch_softmax<P, 4>(stream, M, rowPtrs, a, b, out, bwd);
-    case 8: return launch_softmax<P, 8>(stream, M, rowPtrs, a, b, out, bwd);
-    case 16: return launch_softmax<P, 16>(stream, M, rowPtrs, a, b, out, bwd);
-    case 32: return launch_softmax<P, 32>(stream, M, rowPtrs, a, b, out, bwd);
-    default: return launch_softmax<P, 64>(stream, M, rowPtrs, a, b, out, bwd);
-    }
-}
-
 // forward: a = scores, b unused; backward: a = p, b = dp.  The kernels address through 64-bit pointers, so no array size
 // is declined.
 template <class PRef, class PFast>
 int softmax_csr(const char *name, bool bwd, mispmm_stream_t stream, uint32_t M, uint32_t nnz, const uint32_t *rowPtrs,
                 const typename PRef::T *a, const typename PRef::T *b, typename PRef::T *out, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "%s: unknown accumulate mode %d", name, acc_mode);
+    if (int s = check_acc_mode(name, acc_mode)) return s;
     if (M == 0 || nnz == 0) return MISPMM_OK;
     if (!rowPtrs || !a || (bwd && !b) || !out)
         return fail(MISPMM_ERR_INVALID_ARG, bwd ? "%s: rowPtrs, p, dp or ds is null" : "%s: rowPtrs, scores or out is null", name);
-    if (acc_mode == MISPMM_ACC_REFERENCE) launch_softmax_group<PRef>(as_stream(stream), M, nnz, rowPtrs, a, b, out, bwd);
-    else launch_softmax_group<PFast>(as_stream(stream), M, nnz, rowPtrs, a, b, out, bwd);
+    with_acc<PRef, PFast>(acc_mode, [&](auto acc) {
+        with_const<4, 8, 16, 32, 64>(sm_pick_group(M, nnz), [&](auto g) {
+            launch_softmax<typename decltype(acc)::type, decltype(g)::value>(as_stream(stream), M, rowPtrs, a, b, out, bwd);
+        });
+    });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }

@@ -701,16 +701,6 @@ static void launch_valu(const BsrArgs &a) {
                            a.blocks, a.B, static_cast<uint32_t>(bytes), a.N, a.ldb, a.C, a.ldc);
 }
 
-template <int VEC, class Acc>
-static void launch_valu_g(const BsrArgs &a, int g) {
-    switch (g) {
-        case 8: launch_valu<8, VEC, Acc>(a); break;
-        case 16: launch_valu<16, VEC, Acc>(a); break;
-        case 32: launch_valu<32, VEC, Acc>(a); break;
-        default: launch_valu<64, VEC, Acc>(a); break;
-    }
-}
-
 template <int BD, int VEC, class Acc>
 static void launch_rowblock(const BsrArgs &a) {
     constexpr int RS = BD < 8 ? BD : 8;
@@ -725,26 +715,19 @@ static void launch_rowblock(const BsrArgs &a) {
 // true when the block-row kernel took the launch
 template <class Acc>
 static bool try_rowblock(const BsrArgs &a, int vec) {
-    if (a.bR != a.bC || static_cast<uint64_t>(a.K) * a.ldb * 4u > 0x7FFFFFFFull) return false;
+    if (a.bR != a.bC || !fits_buffer(a.K, a.ldb, 4)) return false;
     if (vec == 4 && a.N <= 128) vec = 2;  // keep all 64 lanes busy at N <= 128
-#define MISPMM_RB_CASE(BD, VV)                  \
-    if (a.bR == BD && vec == VV) {              \
-        launch_rowblock<BD, VV, Acc>(a);        \
-        return true;                            \
-    }
-    MISPMM_RB_CASE(4, 1) MISPMM_RB_CASE(4, 2) MISPMM_RB_CASE(4, 4) MISPMM_RB_CASE(8, 1) MISPMM_RB_CASE(8, 2) MISPMM_RB_CASE(8, 4)
-    MISPMM_RB_CASE(16, 1) MISPMM_RB_CASE(16, 2) MISPMM_RB_CASE(16, 4) MISPMM_RB_CASE(32, 1) MISPMM_RB_CASE(32, 2) MISPMM_RB_CASE(32, 4)
-#undef MISPMM_RB_CASE
-    return false;
+    return try_const<4, 8, 16, 32>(static_cast<int>(a.bR), [&](auto bd) {
+        with_const<1, 2, 4>(vec, [&](auto v) { launch_rowblock<decltype(bd)::value, decltype(v)::value, Acc>(a); });
+    });
 }
 
 template <class Acc>
 static void launch_valu_v(const BsrArgs &a, int vec) {
     if (try_rowblock<Acc>(a, vec)) return;
-    const int g = pick_group(a.N, vec);
-    if (vec == 4) launch_valu_g<4, Acc>(a, g);
-    else if (vec == 2) launch_valu_g<2, Acc>(a, g);
-    else launch_valu_g<1, Acc>(a, g);
+    with_vec(vec, [&](auto v) {
+        with_group(pick_group(a.N, vec), [&](auto g) { launch_valu<decltype(g)::value, decltype(v)::value, Acc>(a); });
+    });
 }
 
 static bool mfma_shape_ok(uint32_t K, uint32_t N, uint32_t ldb, uint32_t ldc, const void *B, const void *C,
@@ -752,7 +735,7 @@ static bool mfma_shape_ok(uint32_t K, uint32_t N, uint32_t ldb, uint32_t ldc, co
     // whole 16-byte (fp32) / 8-byte (bf16) vectors of 4 columns; B must fit a < 2 GiB buffer descriptor
     return N % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && aligned16(blocks) &&
            (reinterpret_cast<uintptr_t>(B) % (4 * elem) == 0) && (reinterpret_cast<uintptr_t>(C) % 8 == 0) &&
-           static_cast<uint64_t>(K) * ldb * elem <= 0x7FFFFFFFull;
+           fits_buffer(K, ldb, static_cast<uint32_t>(elem));
 }
 
 }  // namespace mispmm
@@ -764,8 +747,7 @@ extern "C" int mispmm_bsr_f32(mispmm_stream_t stream, uint32_t numBlockRows, uin
                               const float *blocks, const float *B, uint32_t N, uint32_t ldb, float *C, uint32_t ldc,
                               int kernel, int acc_mode) {
     if (kernel < 0 || kernel > MISPMM_BSR_NUM_KERNELS) return fail(MISPMM_ERR_INVALID_ARG, "bsr: unknown kernel id %d", kernel);
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "bsr: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("bsr", acc_mode)) return s;
     if (bR == 0 || bC == 0) return fail(MISPMM_ERR_INVALID_ARG, "bsr: zero block dimension");
     if (numBlockRows == 0 || N == 0) return MISPMM_OK;
     if (!blockRowPtrs) return fail(MISPMM_ERR_INVALID_ARG, "bsr: blockRowPtrs is null");
@@ -787,8 +769,7 @@ extern "C" int mispmm_bsr_f32(mispmm_stream_t stream, uint32_t numBlockRows, uin
     } else {
         const BsrArgs a{st, numBlockRows, K, bR, bC, blockRowPtrs, blockColIdxs, blocks, B, N, ldb, C, ldc};
         const int vec = pick_vec(B, ldb, C, ldc, N);
-        if (acc_mode == MISPMM_ACC_REFERENCE) launch_valu_v<AccRefF32>(a, vec);
-        else launch_valu_v<AccFast>(a, vec);
+        with_acc<AccRefF32, AccFast>(acc_mode, [&](auto acc) { launch_valu_v<typename decltype(acc)::type>(a, vec); });
     }
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
@@ -813,21 +794,14 @@ extern "C" int mispmm_bsr_bf16(mispmm_stream_t stream, uint32_t numBlockRows, ui
     const XcdGrid xg = xcd_grid(numBlockRows * nST);  // one workgroup per (block row, super-tile)
     dim3 grid(xg.grid);
     const uint32_t b_bytes = static_cast<uint32_t>(static_cast<uint64_t>(K) * ldb * 2u);
-#define MISPMM_BF16_LAUNCH(KERNEL, TPL, CB)                                                                     \
-    hipLaunchKernelGGL((KERNEL<TPL, CB>), grid, dim3(256), 0, as_stream(stream), numBlockRows, nST, blockRowPtrs, \
-                       blockColIdxs, blocks, B, b_bytes, N, ldb, C, ldc, xg.chunk)
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, as_stream(stream), numBlockRows, nST, blockRowPtrs, blockColIdxs, blocks, B, b_bytes, N, ldb,
+                           C, ldc, xg.chunk);
+    };
     // the 128-column kernel runs WITHOUT the register double buffer by default: 72 instead of 104 VGPRs, and the
     // extra resident waves hide the fetch latency better than the prefetch did (13.3 -> 12.2 us on config 4);
     // MISPMM_BSR_PIPE=1 restores the two-deep software pipeline (measurement aid)
     static const bool bsr_pipe = knob_int("MISPMM_BSR_PIPE", 0) == 1;
-#define MISPMM_BF16_PICK(KERNEL)                                                                 \
-    do {                                                                                         \
-        if (wide) {                                                                              \
-            if (c_bf16) MISPMM_BF16_LAUNCH(KERNEL, 8, true); else MISPMM_BF16_LAUNCH(KERNEL, 8, false); \
-        } else {                                                                                 \
-            if (c_bf16) MISPMM_BF16_LAUNCH(KERNEL, 4, true); else MISPMM_BF16_LAUNCH(KERNEL, 4, false); \
-        }                                                                                        \
-    } while (0)
     // MISPMM_BSR_LDS=1: the LDS-staged kernel (bsr_bf16_lds.hpp: LDS-DMA ring + ds_read_b64_tr_b16, the plan of round 1).
     // Passes the same parity tests as the register-staged kernel below but is SLOWER on config 4 (14.9 us at ring depth 4,
     // 15.9 at 6, 18.1 at 8, against 11.4 us; profiles/r2/bsr_bf16_variants.log), so it stays opt-in.
@@ -840,29 +814,32 @@ extern "C" int mispmm_bsr_bf16(mispmm_stream_t stream, uint32_t numBlockRows, ui
         // ring depth 4 (3 block pairs = 15 KiB in flight per workgroup, 8 workgroups per CU); MISPMM_BSR_DEPTH=6|8 deepens it
         static const int depth = knob_int("MISPMM_BSR_DEPTH", 4);
         note_kernel("bsr_bf16_lds<%s,D%d>", c_bf16 ? "c16" : "c32", depth == 4 ? 4 : depth == 6 ? 6 : 8);
-#define MISPMM_LDS_LAUNCH(CB, DD)                                                                                              \
-    hipLaunchKernelGGL((bsr_bf16_lds<CB, DD>), dim3(g.grid), dim3(128), 0, as_stream(stream), numBlockRows, nst, blockRowPtrs, \
-                       blockColIdxs, blocks, static_cast<uint32_t>(blocks_bytes), B, b_bytes, N, ldb, C, ldc, g.chunk)
-        if (depth == 4) {
-            if (c_bf16) MISPMM_LDS_LAUNCH(true, 4); else MISPMM_LDS_LAUNCH(false, 4);
-        } else if (depth == 6) {
-            if (c_bf16) MISPMM_LDS_LAUNCH(true, 6); else MISPMM_LDS_LAUNCH(false, 6);
-        } else {
-            if (c_bf16) MISPMM_LDS_LAUNCH(true, 8); else MISPMM_LDS_LAUNCH(false, 8);
-        }
-#undef MISPMM_LDS_LAUNCH
+        auto launch_lds = [&](auto dd) {
+            with_flag(c_bf16 != 0, [&](auto cb) {
+                hipLaunchKernelGGL((bsr_bf16_lds<decltype(cb)::value, decltype(dd)::value>), dim3(g.grid), dim3(128), 0, as_stream(stream), numBlockRows,
+                                   nst, blockRowPtrs, blockColIdxs, blocks, static_cast<uint32_t>(blocks_bytes), B, b_bytes, N, ldb, C, ldc, g.chunk);
+            });
+        };
+        // plain `if`s on the knob: the production build folds them where they stand and holds host stubs of depth 4 only
+        if (depth == 4) launch_lds(std::integral_constant<int, 4>{});
+        else if (depth == 6) launch_lds(std::integral_constant<int, 6>{});
+        else launch_lds(std::integral_constant<int, 8>{});
         MISPMM_LAUNCH_CHECK();
         return MISPMM_OK;
     }
     // (8 waves per workgroup -- WAVES = 8, half the iterations per wave -- was measured slower: 13.2 vs 11.6 us)
     note_kernel("bsr_mfma_bf16%s<T%d,%s>", bR == 32 ? "_b32" : "", wide ? 8 : 4, c_bf16 ? "c16" : "c32");
     if (bR == 16 && !bsr_pipe && wide) {
-        if (c_bf16) hipLaunchKernelGGL((bsr_mfma_bf16<8, true, false>), grid, dim3(256), 0, as_stream(stream), numBlockRows, nST, blockRowPtrs, blockColIdxs, blocks, B, b_bytes, N, ldb, C, ldc, xg.chunk);
-        else hipLaunchKernelGGL((bsr_mfma_bf16<8, false, false>), grid, dim3(256), 0, as_stream(stream), numBlockRows, nST, blockRowPtrs, blockColIdxs, blocks, B, b_bytes, N, ldb, C, ldc, xg.chunk);
-    } else if (bR == 16) MISPMM_BF16_PICK(bsr_mfma_bf16);
-    else MISPMM_BF16_PICK(bsr_mfma_bf16_b32);
-#undef MISPMM_BF16_PICK
-#undef MISPMM_BF16_LAUNCH
+        with_flag(c_bf16 != 0, [&](auto cb) { launch(bsr_mfma_bf16<8, decltype(cb)::value, false>); });
+    } else if (bR == 16) {
+        with_const<8, 4>(wide ? 8 : 4, [&](auto tpl) {
+            with_flag(c_bf16 != 0, [&](auto cb) { launch(bsr_mfma_bf16<decltype(tpl)::value, decltype(cb)::value>); });
+        });
+    } else {
+        with_const<8, 4>(wide ? 8 : 4, [&](auto tpl) {
+            with_flag(c_bf16 != 0, [&](auto cb) { launch(bsr_mfma_bf16_b32<decltype(tpl)::value, decltype(cb)::value>); });
+        });
+    }
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
@@ -875,18 +852,16 @@ extern "C" int mispmm_bsrc_bf16(mispmm_stream_t stream, uint32_t numBlockRows, u
     if (nSteps != 0 && (!cols || !tiles)) return fail(MISPMM_ERR_INVALID_ARG, "bsrc_bf16: null step arrays");
     if (ldb < N || ldc < N) return fail(MISPMM_ERR_INVALID_ARG, "bsrc_bf16: leading dimension smaller than N");
     if (N % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0 || !aligned16(B) || !aligned16(C) || !aligned16(tiles) || !aligned16(cols) ||
-        static_cast<uint64_t>(K) * ldb * 2u > 0x7FFFFFFFull)
+        !fits_buffer(K, ldb, 2))
         return fail(MISPMM_ERR_UNSUPPORTED, "bsrc_bf16: N / ldb / ldc must be multiples of 8, operands 16-byte aligned, B below 2 GiB");
     const uint32_t nST = ceil_div(N, 128u);
     const XcdGrid xg = xcd_grid(ceil_div(numBlockRows * nST, 4u));
     const uint32_t b_bytes = static_cast<uint32_t>(static_cast<uint64_t>(K) * ldb * 2u);
     note_kernel("bsrc_mfma_bf16<%s>", c_bf16 ? "c16" : "c32");
-    if (c_bf16)
-        hipLaunchKernelGGL((bsrc_mfma_bf16<true>), dim3(xg.grid), dim3(256), 0, as_stream(stream), numBlockRows, nST, stepPtrs, cols, tiles,
-                           B, b_bytes, N, ldb, C, ldc, xg.chunk);
-    else
-        hipLaunchKernelGGL((bsrc_mfma_bf16<false>), dim3(xg.grid), dim3(256), 0, as_stream(stream), numBlockRows, nST, stepPtrs, cols, tiles,
-                           B, b_bytes, N, ldb, C, ldc, xg.chunk);
+    with_flag(c_bf16 != 0, [&](auto cb) {
+        hipLaunchKernelGGL((bsrc_mfma_bf16<decltype(cb)::value>), dim3(xg.grid), dim3(256), 0, as_stream(stream), numBlockRows, nST, stepPtrs, cols,
+                           tiles, B, b_bytes, N, ldb, C, ldc, xg.chunk);
+    });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
@@ -904,7 +879,7 @@ extern "C" int mispmm_bsrc_slots_bf16(mispmm_stream_t stream, uint32_t numBlockR
         return fail(MISPMM_ERR_UNSUPPORTED, "bsrc_slots_bf16: %u block rows x %u columns exceed the grid of this kernel", numBlockRows, N);
     if (ldb < N || ldc < N) return fail(MISPMM_ERR_INVALID_ARG, "bsrc_slots_bf16: leading dimension smaller than N");
     if (N % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0 || !aligned16(B) || !aligned16(C) || !aligned16(tiles) || !aligned16(cols) ||
-        static_cast<uint64_t>(K) * ldb * 2u > 0x7FFFFFFFull)
+        !fits_buffer(K, ldb, 2))
         return fail(MISPMM_ERR_UNSUPPORTED, "bsrc_slots_bf16: N / ldb / ldc must be multiples of 8, operands 16-byte aligned, B below 2 GiB");
     const uint32_t nST = ceil_div(N, 128u);
     const XcdGrid xg = xcd_grid(numBlockRows * nST);  // one workgroup per (block row, 128 columns)
@@ -924,23 +899,15 @@ extern "C" int mispmm_bsrc_slots_bf16(mispmm_stream_t stream, uint32_t numBlockR
     const bool share = nSteps == slot_steps && (share_knob == 2 || (share_knob == 1 && !c_bf16));
     note_kernel("bsrc_slots_mfma_bf16<%s,%s%s>", c_bf16 ? "c16" : "c32", st == 2 ? "nt" : st == 16 ? "sc1" : st == 18 ? "sc1nt" : "plain",
                 share ? ",share" : "");
-#define MISPMM_SLOTS_LAUNCH(CB, ST, SH)                                                                                            \
-    hipLaunchKernelGGL((bsrc_slots_mfma_bf16<CB, ST, SH>), dim3(xg.grid), dim3(256), 0, as_stream(stream), numBlockRows, nST, extraPtrs, \
-                       cols, tiles, B, b_bytes, N, ldb, C, static_cast<uint32_t>(st >= 0 ? c_bytes : 0), ldc, xg.chunk)
-#define MISPMM_SLOTS_PICK(CB, SH)                        \
-    do {                                                 \
-        if (st == 2) MISPMM_SLOTS_LAUNCH(CB, 2, SH);     \
-        else if (st == 16) MISPMM_SLOTS_LAUNCH(CB, 16, SH); \
-        else if (st == 18) MISPMM_SLOTS_LAUNCH(CB, 18, SH); \
-        else MISPMM_SLOTS_LAUNCH(CB, -1, SH);            \
-    } while (0)
-    if (share) {
-        if (c_bf16) MISPMM_SLOTS_PICK(true, true); else MISPMM_SLOTS_PICK(false, true);
-    } else {
-        if (c_bf16) MISPMM_SLOTS_PICK(true, false); else MISPMM_SLOTS_PICK(false, false);
-    }
-#undef MISPMM_SLOTS_PICK
-#undef MISPMM_SLOTS_LAUNCH
+    with_flag(share, [&](auto sh) {
+        with_flag(c_bf16 != 0, [&](auto cb) {
+            with_const<2, 16, 18, -1>(st, [&](auto pol) {
+                hipLaunchKernelGGL((bsrc_slots_mfma_bf16<decltype(cb)::value, decltype(pol)::value, decltype(sh)::value>), dim3(xg.grid), dim3(256), 0,
+                                   as_stream(stream), numBlockRows, nST, extraPtrs, cols, tiles, B, b_bytes, N, ldb, C,
+                                   static_cast<uint32_t>(st >= 0 ? c_bytes : 0), ldc, xg.chunk);
+            });
+        });
+    });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }

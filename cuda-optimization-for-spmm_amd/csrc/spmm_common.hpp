@@ -4,6 +4,7 @@
 #include <type_traits>
 #include <cstdlib>
 
+#include "dispatch.hpp"
 #include "mispmm_internal.hpp"
 
 namespace mispmm {
@@ -196,6 +197,21 @@ inline int pick_group(uint32_t N, int vec) {
     int g = 8;
     while (g < 64 && static_cast<uint32_t>(g) < need) g <<= 1;
     return g;
+}
+
+// rows * ld elements of elem_bytes fit a raw buffer descriptor: less than 2 GiB, bit 31 of an offset marks a dropped load
+inline bool fits_buffer(uint64_t rows, uint32_t ld, uint32_t elem_bytes) { return rows * ld * elem_bytes <= 0x7FFFFFFFull; }
+
+inline int check_acc_mode(const char *name, int acc_mode) {
+    if (acc_mode == MISPMM_ACC_REFERENCE || acc_mode == MISPMM_ACC_FAST) return MISPMM_OK;
+    return fail(MISPMM_ERR_INVALID_ARG, "%s: unknown accumulate mode %d", name, acc_mode);
+}
+
+// one row list (rowPtrs[M + 1], colIdxs[nnz], vals[nnz])
+inline int check_row_list(const char *name, const uint32_t *rowPtrs, uint32_t nnz, const uint32_t *colIdxs, const void *vals) {
+    if (!rowPtrs) return fail(MISPMM_ERR_INVALID_ARG, "%s: rowPtrs is null", name);
+    if (nnz != 0 && (!colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "%s: colIdxs or vals is null", name);
+    return MISPMM_OK;
 }
 
 inline int check_dense_args(const float *B, uint32_t N, uint32_t ldb, const float *C, uint32_t ldc) {

@@ -131,24 +131,6 @@ static void launch_coo(const CooArgs &a) {
                            a.colIdxs, a.vals, a.B, static_cast<uint32_t>(bytes), a.N, a.ldb, a.C, a.ldc);
 }
 
-template <int VEC, class Acc>
-static void launch_coo_g(const CooArgs &a, int g) {
-    switch (g) {
-        case 8: launch_coo<8, VEC, Acc>(a); break;
-        case 16: launch_coo<16, VEC, Acc>(a); break;
-        case 32: launch_coo<32, VEC, Acc>(a); break;
-        default: launch_coo<64, VEC, Acc>(a); break;
-    }
-}
-
-template <class Acc>
-static void launch_coo_v(const CooArgs &a, int vec) {
-    const int g = pick_group(a.N, vec);
-    if (vec == 4) launch_coo_g<4, Acc>(a, g);
-    else if (vec == 2) launch_coo_g<2, Acc>(a, g);
-    else launch_coo_g<1, Acc>(a, g);
-}
-
 // Rows with their boundaries materialised (prepared-bounds COO, the BSR non-zero list), fp32 arithmetic.  Long rows
 // (24 entries per row or more on average) of 16-byte B vectors take the split kernel's shape: one wave per row x 32
 // columns on the XCD column grid, 64 entries in flight -- summed in entry order in REFERENCE mode (fp32 product, fp32 add:
@@ -169,6 +151,14 @@ static void launch_rows(hipStream_t st, uint32_t M, uint32_t K, uint32_t nnz, co
     launch_row_gather_auto<Acc>(ga, CsrRows{rowPtrs}, vec);
 }
 
+static void launch_rows(int acc_mode, hipStream_t st, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs, const uint32_t *colIdxs,
+                        const float *vals, const float *B, uint32_t N, uint32_t ldb, float *C, uint32_t ldc, int vec,
+                        const uint32_t *spans = nullptr) {
+    with_acc<AccRefF32, AccFast>(acc_mode, [&](auto acc) {
+        launch_rows<typename decltype(acc)::type>(st, M, K, nnz, rowPtrs, colIdxs, vals, B, N, ldb, C, ldc, vec, spans);
+    });
+}
+
 }  // namespace mispmm
 
 using namespace mispmm;
@@ -186,8 +176,7 @@ extern "C" int mispmm_coo_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, ui
                               const uint32_t *colIdxs, const float *vals, const float *B, uint32_t N, uint32_t ldb,
                               float *C, uint32_t ldc, uint32_t *rowPtrs_workspace, int kernel, int acc_mode) {
     if (kernel < 0 || kernel > MISPMM_COO_NUM_KERNELS) return fail(MISPMM_ERR_INVALID_ARG, "coo: unknown kernel id %d", kernel);
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "coo: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("coo", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
     if (nnz != 0 && (!rowIdxs || !colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "coo: null index or value array");
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
@@ -200,15 +189,16 @@ extern "C" int mispmm_coo_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, ui
     }
     const CooArgs a{st, M, K, nnz, rowIdxs, rowPtrs_workspace, colIdxs, vals, B, N, ldb, C, ldc};
     const int vec = pick_vec(B, ldb, C, ldc, N);
-    if (rowPtrs_workspace && static_cast<uint64_t>(K) * ldb * 4u <= 0x7FFFFFFFull) {
+    if (rowPtrs_workspace && fits_buffer(K, ldb, 4)) {
         // with its row bounds materialised a sorted COO is a CSR: same kernel, same order of sums
-        if (acc_mode == MISPMM_ACC_REFERENCE) launch_rows<AccRefF32>(st, M, K, nnz, rowPtrs_workspace, colIdxs, vals, B, N, ldb, C, ldc, vec);
-        else launch_rows<AccFast>(st, M, K, nnz, rowPtrs_workspace, colIdxs, vals, B, N, ldb, C, ldc, vec);
-        MISPMM_LAUNCH_CHECK();
-        return MISPMM_OK;
+        launch_rows(acc_mode, st, M, K, nnz, rowPtrs_workspace, colIdxs, vals, B, N, ldb, C, ldc, vec);
+    } else {
+        with_acc<AccRefF32, AccFast>(acc_mode, [&](auto acc) {
+            with_vec(vec, [&](auto v) {
+                with_group(pick_group(N, vec), [&](auto g) { launch_coo<decltype(g)::value, decltype(v)::value, typename decltype(acc)::type>(a); });
+            });
+        });
     }
-    if (acc_mode == MISPMM_ACC_REFERENCE) launch_coo_v<AccRefF32>(a, vec);
-    else launch_coo_v<AccFast>(a, vec);
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
@@ -219,17 +209,15 @@ extern "C" int mispmm_coo_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, ui
 extern "C" int mispmm_rows_split_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *colIdxs,
                                      const float *vals, const uint32_t *spans, uint32_t numSpans, const float *B, uint32_t N,
                                      uint32_t ldb, float *C, uint32_t ldc, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "rows_split: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("rows_split", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
     if (!spans || !aligned16(spans)) return fail(MISPMM_ERR_INVALID_ARG, "rows_split: spans is null or not 16-byte aligned");
     if (numSpans != M) return fail(MISPMM_ERR_INVALID_ARG, "rows_split: %u spans for %u rows (one per row: share_len = 0xFFFFFFFF)", numSpans, M);
     if (nnz != 0 && (!colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "rows_split: colIdxs or vals is null");
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
-    if (static_cast<uint64_t>(K) * ldb * 4u > 0x7FFFFFFFull) return fail(MISPMM_ERR_UNSUPPORTED, "rows_split: B of 2 GiB or more");
+    if (!fits_buffer(K, ldb, 4)) return fail(MISPMM_ERR_UNSUPPORTED, "rows_split: B of 2 GiB or more");
     if (pick_vec(B, ldb, C, ldc, N) != 4) return fail(MISPMM_ERR_UNSUPPORTED, "rows_split: B and C rows must be 16-byte vectors");
-    if (acc_mode == MISPMM_ACC_REFERENCE) launch_rows<AccRefF32>(as_stream(stream), M, K, nnz, nullptr, colIdxs, vals, B, N, ldb, C, ldc, 4, spans);
-    else launch_rows<AccFast>(as_stream(stream), M, K, nnz, nullptr, colIdxs, vals, B, N, ldb, C, ldc, 4, spans);
+    launch_rows(acc_mode, as_stream(stream), M, K, nnz, nullptr, colIdxs, vals, B, N, ldb, C, ldc, 4, spans);
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
@@ -240,8 +228,7 @@ extern "C" int mispmm_rows_split_f32(mispmm_stream_t stream, uint32_t M, uint32_
 extern "C" int mispmm_rows_hybrid_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *colIdxs, const float *vals,
                                       const uint32_t *spans, uint32_t numSpans, uint32_t numLongSpans, const float *B, uint32_t N,
                                       uint32_t ldb, float *C, uint32_t ldc, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "rows_hybrid: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("rows_hybrid", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
     if (!spans || !aligned16(spans)) return fail(MISPMM_ERR_INVALID_ARG, "rows_hybrid: spans is null or not 16-byte aligned");
     if (numSpans != M) return fail(MISPMM_ERR_INVALID_ARG, "rows_hybrid: %u spans for %u rows (one per row: share_len = 0xFFFFFFFF)", numSpans, M);
@@ -249,10 +236,9 @@ extern "C" int mispmm_rows_hybrid_f32(mispmm_stream_t stream, uint32_t M, uint32
         return fail(MISPMM_ERR_INVALID_ARG, "rows_hybrid: %u long spans of %u: a multiple of 4 is needed", numLongSpans, numSpans);
     if (nnz != 0 && (!colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "rows_hybrid: colIdxs or vals is null");
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
-    if (static_cast<uint64_t>(K) * ldb * 4u > 0x7FFFFFFFull || pick_vec(B, ldb, C, ldc, N) != 4) return MISPMM_ERR_UNSUPPORTED;
+    if (!fits_buffer(K, ldb, 4) || pick_vec(B, ldb, C, ldc, N) != 4) return MISPMM_ERR_UNSUPPORTED;
     const HybridArgs a{as_stream(stream), M, K, colIdxs, vals, B, N, ldb, C, ldc, spans, numSpans, numLongSpans};
-    const bool taken = acc_mode == MISPMM_ACC_REFERENCE ? launch_hybrid<AccRefF32>(a) : launch_hybrid<AccFast>(a);
-    if (!taken) return MISPMM_ERR_UNSUPPORTED;
+    if (!with_acc<AccRefF32, AccFast>(acc_mode, [&](auto acc) { return launch_hybrid<typename decltype(acc)::type>(a); })) return MISPMM_ERR_UNSUPPORTED;
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
@@ -261,17 +247,13 @@ extern "C" int mispmm_rows_hybrid_f32(mispmm_stream_t stream, uint32_t M, uint32
 extern "C" int mispmm_ell_compact_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs,
                                       const uint32_t *colIdxs, const float *vals, const float *B, uint32_t N, uint32_t ldb,
                                       float *C, uint32_t ldc, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "ell_compact: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("ell_compact", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
-    if (!rowPtrs) return fail(MISPMM_ERR_INVALID_ARG, "ell_compact: rowPtrs is null");
-    if (nnz != 0 && (!colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "ell_compact: colIdxs or vals is null");
+    if (int s = check_row_list("ell_compact", rowPtrs, nnz, colIdxs, vals)) return s;
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
-    if (static_cast<uint64_t>(K) * ldb * 4u > 0x7FFFFFFFull)
-        return fail(MISPMM_ERR_UNSUPPORTED, "ell_compact: B of 2 GiB or more: use mispmm_ell_f32");
+    if (!fits_buffer(K, ldb, 4)) return fail(MISPMM_ERR_UNSUPPORTED, "ell_compact: B of 2 GiB or more: use mispmm_ell_f32");
     const int vec = pick_vec(B, ldb, C, ldc, N);
-    if (acc_mode == MISPMM_ACC_REFERENCE) launch_rows<AccRefF32>(as_stream(stream), M, K, nnz, rowPtrs, colIdxs, vals, B, N, ldb, C, ldc, vec);
-    else launch_rows<AccFast>(as_stream(stream), M, K, nnz, rowPtrs, colIdxs, vals, B, N, ldb, C, ldc, vec);
+    launch_rows(acc_mode, as_stream(stream), M, K, nnz, rowPtrs, colIdxs, vals, B, N, ldb, C, ldc, vec);
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
@@ -282,17 +264,13 @@ extern "C" int mispmm_ell_compact_f32(mispmm_stream_t stream, uint32_t M, uint32
 extern "C" int mispmm_bsr_nonzeros_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs,
                                        const uint32_t *colIdxs, const float *vals, const float *B, uint32_t N, uint32_t ldb,
                                        float *C, uint32_t ldc, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "bsr_nonzeros: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("bsr_nonzeros", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
-    if (!rowPtrs) return fail(MISPMM_ERR_INVALID_ARG, "bsr_nonzeros: rowPtrs is null");
-    if (nnz != 0 && (!colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "bsr_nonzeros: colIdxs or vals is null");
+    if (int s = check_row_list("bsr_nonzeros", rowPtrs, nnz, colIdxs, vals)) return s;
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
-    if (static_cast<uint64_t>(K) * ldb * 4u > 0x7FFFFFFFull)
-        return fail(MISPMM_ERR_UNSUPPORTED, "bsr_nonzeros: B of 2 GiB or more: use mispmm_bsr_f32");
+    if (!fits_buffer(K, ldb, 4)) return fail(MISPMM_ERR_UNSUPPORTED, "bsr_nonzeros: B of 2 GiB or more: use mispmm_bsr_f32");
     const int vec = pick_vec(B, ldb, C, ldc, N);
-    if (acc_mode == MISPMM_ACC_REFERENCE) launch_rows<AccRefF32>(as_stream(stream), M, K, nnz, rowPtrs, colIdxs, vals, B, N, ldb, C, ldc, vec);
-    else launch_rows<AccFast>(as_stream(stream), M, K, nnz, rowPtrs, colIdxs, vals, B, N, ldb, C, ldc, vec);
+    launch_rows(acc_mode, as_stream(stream), M, K, nnz, rowPtrs, colIdxs, vals, B, N, ldb, C, ldc, vec);
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }

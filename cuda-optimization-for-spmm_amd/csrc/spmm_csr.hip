@@ -498,16 +498,6 @@ static void launch_grouped(const CsrArgs &a, int kernel, bool wide) {
                            b_bytes, a.N, a.ldb, a.C, a.ldc, xg.chunk);
 }
 
-template <int VEC, class Acc>
-static void launch_grouped_g(const CsrArgs &a, int kernel, int g, bool wide) {
-    switch (g) {
-        case 8: launch_grouped<8, VEC, Acc>(a, kernel, wide); break;
-        case 16: launch_grouped<16, VEC, Acc>(a, kernel, wide); break;
-        case 32: launch_grouped<32, VEC, Acc>(a, kernel, wide); break;
-        default: launch_grouped<64, VEC, Acc>(a, kernel, wide); break;
-    }
-}
-
 template <int VEC, int ROWS, class Acc>
 static void launch_wave(const CsrArgs &a) {
     const XcdGrid xg = xcd_grid(ceil_div(a.M, 4 * ROWS));
@@ -541,7 +531,7 @@ template <class Acc>
 static void launch_csr(const CsrArgs &a, int kernel, int vec) {
     // buffer offsets are 32-bit and bit 31 marks a dropped load: a B of 2 GiB or more takes the
     // 64-bit-address kernel
-    const bool wide = static_cast<uint64_t>(a.K) * a.ldb * 4u > 0x7FFFFFFFull;
+    const bool wide = !fits_buffer(a.K, a.ldb, 4);
     // kernel 5 on a matrix whose MEAN row is long (nnz >= 24 M): the deep wave-per-row kernel.  MISPMM_LONGROWS=0/1
     // forces the choice (measurement aid; results do not depend on it).
     static const int long_env = knob_int("MISPMM_LONGROWS", -1);
@@ -570,9 +560,7 @@ static void launch_csr(const CsrArgs &a, int kernel, int vec) {
         while (v > 1 && 64u * (v / 2) >= a.N) v /= 2;
         static const int vec_env = knob_int("MISPMM_LONGROWS_VEC", 0);
         if (vec_env > 0) v = min(v, vec_env);
-        if (v == 4) launch_wave_deep<4, Acc>(a);
-        else if (v == 2) launch_wave_deep<2, Acc>(a);
-        else launch_wave_deep<1, Acc>(a);
+        with_vec(v, [&](auto vv) { launch_wave_deep<decltype(vv)::value, Acc>(a); });
         return;
     }
     if (kernel == 5 && !wide) {
@@ -582,23 +570,16 @@ static void launch_csr(const CsrArgs &a, int kernel, int vec) {
         return;
     }
     if (kernel == 1 || kernel == 2 || kernel == 5 || wide) {
-        const int g = pick_group(a.N, vec);
-        if (vec == 4) launch_grouped_g<4, Acc>(a, kernel, g, wide);
-        else if (vec == 2) launch_grouped_g<2, Acc>(a, kernel, g, wide);
-        else launch_grouped_g<1, Acc>(a, kernel, g, wide);
+        with_vec(vec, [&](auto v) {
+            with_group(pick_group(a.N, vec), [&](auto g) { launch_grouped<decltype(g)::value, decltype(v)::value, Acc>(a, kernel, wide); });
+        });
         return;
     }
     // wave per row: narrow the vector so a 64-lane wave is not mostly idle at small N
     while (vec > 1 && 64u * (vec / 2) >= a.N) vec /= 2;
-    if (kernel == 3) {
-        if (vec == 4) launch_wave<4, 1, Acc>(a);
-        else if (vec == 2) launch_wave<2, 1, Acc>(a);
-        else launch_wave<1, 1, Acc>(a);
-    } else {
-        if (vec == 4) launch_wave<4, 2, Acc>(a);
-        else if (vec == 2) launch_wave<2, 2, Acc>(a);
-        else launch_wave<1, 2, Acc>(a);
-    }
+    with_const<1, 2>(kernel == 3 ? 1 : 2, [&](auto rows) {  // kernel 4: two rows in flight per wave
+        with_vec(vec, [&](auto v) { launch_wave<decltype(v)::value, decltype(rows)::value, Acc>(a); });
+    });
 }
 
 }  // namespace mispmm
@@ -633,14 +614,12 @@ extern "C" int mispmm_debug_row_line_fits(uint32_t M, uint32_t width, uint32_t l
 extern "C" int mispmm_csr_uniform_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t rowNnz,
                                       const uint32_t *colIdxs, const float *vals, const float *B, uint32_t N, uint32_t ldb,
                                       float *C, uint32_t ldc, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "csr_uniform: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("csr_uniform", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
     if (rowNnz != 0 && (!colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "csr_uniform: colIdxs or vals is null");
     if (static_cast<uint64_t>(M) * rowNnz > 0xFFFFFFFFull) return fail(MISPMM_ERR_INVALID_ARG, "csr_uniform: more than 2^32 entries");
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
-    if (static_cast<uint64_t>(K) * ldb * 4u > 0x7FFFFFFFull)
-        return fail(MISPMM_ERR_UNSUPPORTED, "csr_uniform: B of 2 GiB or more: use mispmm_csr_f32");
+    if (!fits_buffer(K, ldb, 4)) return fail(MISPMM_ERR_UNSUPPORTED, "csr_uniform: B of 2 GiB or more: use mispmm_csr_f32");
     const RowGatherArgs ga{as_stream(stream), M, K, colIdxs, vals, B, N, ldb, C, ldc};
     const int vec = pick_vec(B, ldb, C, ldc, N);
     // more than one round of waves: the persistent row-walking launch (row_stream.hpp)
@@ -648,8 +627,7 @@ extern "C" int mispmm_csr_uniform_f32(mispmm_stream_t stream, uint32_t M, uint32
         MISPMM_LAUNCH_CHECK();
         return MISPMM_OK;
     }
-    if (acc_mode == MISPMM_ACC_REFERENCE) launch_row_gather_auto<AccRefWide>(ga, UniformRows{rowNnz}, vec);
-    else launch_row_gather_auto<AccFast>(ga, UniformRows{rowNnz}, vec);
+    with_acc<AccRefWide, AccFast>(acc_mode, [&](auto acc) { launch_row_gather_auto<typename decltype(acc)::type>(ga, UniformRows{rowNnz}, vec); });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
@@ -658,17 +636,14 @@ extern "C" int mispmm_csr_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, ui
                               const uint32_t *colIdxs, const float *vals, const float *B, uint32_t N, uint32_t ldb,
                               float *C, uint32_t ldc, int kernel, int acc_mode) {
     if (kernel < 0 || kernel > MISPMM_CSR_NUM_KERNELS) return fail(MISPMM_ERR_INVALID_ARG, "csr: unknown kernel id %d", kernel);
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "csr: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("csr", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
-    if (!rowPtrs) return fail(MISPMM_ERR_INVALID_ARG, "csr: rowPtrs is null");
-    if (nnz != 0 && (!colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "csr: colIdxs or vals is null");
+    if (int s = check_row_list("csr", rowPtrs, nnz, colIdxs, vals)) return s;
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
     if (kernel == MISPMM_KERNEL_AUTO) kernel = 5;
     const CsrArgs a{as_stream(stream), M, K, rowPtrs, colIdxs, vals, B, N, ldb, C, ldc, nnz};
     const int vec = pick_vec(B, ldb, C, ldc, N);
-    if (acc_mode == MISPMM_ACC_REFERENCE) launch_csr<AccRefWide>(a, kernel, vec);
-    else launch_csr<AccFast>(a, kernel, vec);
+    with_acc<AccRefWide, AccFast>(acc_mode, [&](auto acc) { launch_csr<typename decltype(acc)::type>(a, kernel, vec); });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
@@ -678,8 +653,7 @@ extern "C" int mispmm_csr_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, ui
 extern "C" int mispmm_csr_split_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs,
                                     const uint32_t *colIdxs, const float *vals, const uint32_t *spans, uint32_t numSpans,
                                     const float *B, uint32_t N, uint32_t ldb, float *C, uint32_t ldc, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "csr_split: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("csr_split", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
     if (!rowPtrs && !spans) return fail(MISPMM_ERR_INVALID_ARG, "csr_split: rowPtrs and spans are both null");
     if (!aligned16(spans)) return fail(MISPMM_ERR_INVALID_ARG, "csr_split: spans must be 16-byte aligned");
@@ -687,14 +661,13 @@ extern "C" int mispmm_csr_split_f32(mispmm_stream_t stream, uint32_t M, uint32_t
         return fail(MISPMM_ERR_INVALID_ARG, "csr_split: %u spans cannot describe %u rows (M + 3 per shared row)", numSpans, M);
     if (nnz != 0 && (!colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "csr_split: colIdxs or vals is null");
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
-    if (static_cast<uint64_t>(K) * ldb * 4u > 0x7FFFFFFFull) return fail(MISPMM_ERR_UNSUPPORTED, "csr_split: B of 2 GiB or more: use mispmm_csr_f32");
+    if (!fits_buffer(K, ldb, 4)) return fail(MISPMM_ERR_UNSUPPORTED, "csr_split: B of 2 GiB or more: use mispmm_csr_f32");
     if (pick_vec(B, ldb, C, ldc, N) != 4)
         return fail(MISPMM_ERR_UNSUPPORTED, "csr_split: B and C rows must be 16-byte vectors (N, ldb, ldc multiples of 4, aligned): use mispmm_csr_f32");
     CsrArgs a{as_stream(stream), M, K, rowPtrs, colIdxs, vals, B, N, ldb, C, ldc, nnz};
     a.spans = spans;
     a.numSpans = numSpans;
-    if (acc_mode == MISPMM_ACC_REFERENCE) launch_split<AccRefWide>(a);
-    else launch_split<AccFast>(a);
+    with_acc<AccRefWide, AccFast>(acc_mode, [&](auto acc) { launch_split<typename decltype(acc)::type>(a); });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
@@ -705,8 +678,7 @@ extern "C" int mispmm_csr_split_f32(mispmm_stream_t stream, uint32_t M, uint32_t
 extern "C" int mispmm_csr_hybrid_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *colIdxs, const float *vals,
                                      const uint32_t *spans, uint32_t numSpans, uint32_t numLongSpans, const float *B, uint32_t N,
                                      uint32_t ldb, float *C, uint32_t ldc, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "csr_hybrid: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("csr_hybrid", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
     if (!spans || !aligned16(spans)) return fail(MISPMM_ERR_INVALID_ARG, "csr_hybrid: spans must be a 16-byte aligned device array");
     if (numSpans < M || (numSpans - M) % 3u != 0)
@@ -716,10 +688,9 @@ extern "C" int mispmm_csr_hybrid_f32(mispmm_stream_t stream, uint32_t M, uint32_
                     (numSpans - M) / 3u);
     if (nnz != 0 && (!colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "csr_hybrid: colIdxs or vals is null");
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
-    if (static_cast<uint64_t>(K) * ldb * 4u > 0x7FFFFFFFull || pick_vec(B, ldb, C, ldc, N) != 4) return MISPMM_ERR_UNSUPPORTED;
+    if (!fits_buffer(K, ldb, 4) || pick_vec(B, ldb, C, ldc, N) != 4) return MISPMM_ERR_UNSUPPORTED;
     const HybridArgs a{as_stream(stream), M, K, colIdxs, vals, B, N, ldb, C, ldc, spans, numSpans, numLongSpans};
-    const bool taken = acc_mode == MISPMM_ACC_REFERENCE ? launch_hybrid<AccRefWide>(a) : launch_hybrid<AccFast>(a);
-    if (!taken) return MISPMM_ERR_UNSUPPORTED;
+    if (!with_acc<AccRefWide, AccFast>(acc_mode, [&](auto acc) { return launch_hybrid<typename decltype(acc)::type>(a); })) return MISPMM_ERR_UNSUPPORTED;
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
@@ -732,14 +703,22 @@ extern "C" int mispmm_debug_set_stamps_split(void *device_buffer) {
 }
 #endif
 
+// the row-gather kernel on rows of one length (uniformRowNnz > 0) or on the row pointers
+static void launch_row_gather_auto(int acc_mode, const RowGatherArgs &ga, uint32_t uniformRowNnz, const uint32_t *rowPtrs, int vec) {
+    with_acc<AccRefWide, AccFast>(acc_mode, [&](auto acc) {
+        using Acc = typename decltype(acc)::type;
+        if (uniformRowNnz) launch_row_gather_auto<Acc>(ga, UniformRows{uniformRowNnz}, vec);
+        else launch_row_gather_auto<Acc>(ga, CsrRows{rowPtrs}, vec);
+    });
+}
+
 // Several dense operands, one launch.  Only the row-gather kernel has a batched form; shapes it does not take
 // (a B of 2 GiB or more, rows too long for it, operands that are not 16-byte vectors) go out as one launch each.
 extern "C" int mispmm_csr_batch_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs,
                                     const uint32_t *colIdxs, const float *vals, uint32_t uniformRowNnz, uint32_t batch,
                                     const float *const *B_list_host, uint32_t N, uint32_t ldb, float *const *C_list_host,
                                     uint32_t ldc, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "csr_batch: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("csr_batch", acc_mode)) return s;
     if (batch == 0 || M == 0 || N == 0) return MISPMM_OK;
     if (!B_list_host || !C_list_host) return fail(MISPMM_ERR_INVALID_ARG, "csr_batch: null operand list");
     if (!rowPtrs && uniformRowNnz == 0) return fail(MISPMM_ERR_INVALID_ARG, "csr_batch: rowPtrs is null");
@@ -750,7 +729,7 @@ extern "C" int mispmm_csr_batch_f32(mispmm_stream_t stream, uint32_t M, uint32_t
         vec = std::min(vec, pick_vec(B_list_host[i], ldb, C_list_host[i], ldc, N));
     }
     const bool long_rows = uniformRowNnz == 0 && nnz / M >= 24;
-    const bool fits = static_cast<uint64_t>(K) * ldb * 4u <= 0x7FFFFFFFull && static_cast<uint64_t>(M) * ldc * 4u <= 0x7FFFFFFFull;
+    const bool fits = fits_buffer(K, ldb, 4) && fits_buffer(M, ldc, 4);
     const uint32_t cpp = N / xcd_tiling(N, vec, K).q;
     if (vec != 4 || !fits || long_rows || (cpp % 32 != 0)) {  // no batched kernel for this shape: one launch per operand
         for (uint32_t i = 0; i < batch; ++i) {
@@ -768,13 +747,7 @@ extern "C" int mispmm_csr_batch_f32(mispmm_stream_t stream, uint32_t M, uint32_t
         ga.B_list = B_list_host + first;
         ga.C_list = C_list_host + first;
         ga.row_len_guess = uniform_guess(M, nnz);
-        if (uniformRowNnz) {
-            if (acc_mode == MISPMM_ACC_REFERENCE) launch_row_gather_auto<AccRefWide>(ga, UniformRows{uniformRowNnz}, vec);
-            else launch_row_gather_auto<AccFast>(ga, UniformRows{uniformRowNnz}, vec);
-        } else {
-            if (acc_mode == MISPMM_ACC_REFERENCE) launch_row_gather_auto<AccRefWide>(ga, CsrRows{rowPtrs}, vec);
-            else launch_row_gather_auto<AccFast>(ga, CsrRows{rowPtrs}, vec);
-        }
+        launch_row_gather_auto(acc_mode, ga, uniformRowNnz, rowPtrs, vec);
         MISPMM_LAUNCH_CHECK();
     }
     return MISPMM_OK;
@@ -787,8 +760,7 @@ extern "C" int mispmm_csr_plan_f32(mispmm_stream_t stream, uint32_t M, uint32_t 
                                    const uint32_t *colIdxs, const float *vals, uint32_t uniformRowNnz, const uint32_t *rowMap,
                                    uint32_t batch, const float *const *B_list_host, uint32_t N, uint32_t ldb,
                                    float *const *C_list_host, uint32_t ldc, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "csr_plan: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("csr_plan", acc_mode)) return s;
     if (batch == 0 || M == 0 || N == 0) return MISPMM_OK;
     if (!B_list_host || !C_list_host) return fail(MISPMM_ERR_INVALID_ARG, "csr_plan: null operand list");
     if (!rowPtrs && uniformRowNnz == 0) return fail(MISPMM_ERR_INVALID_ARG, "csr_plan: rowPtrs is null");
@@ -798,25 +770,19 @@ extern "C" int mispmm_csr_plan_f32(mispmm_stream_t stream, uint32_t M, uint32_t 
         if (int s = check_dense_args(B_list_host[i], N, ldb, C_list_host[i], ldc)) return s;
         vec = std::min(vec, pick_vec(B_list_host[i], ldb, C_list_host[i], ldc, N));
     }
-    if (static_cast<uint64_t>(K) * ldb * 4u > 0x7FFFFFFFull)
+    if (!fits_buffer(K, ldb, 4))
         return fail(MISPMM_ERR_UNSUPPORTED, "csr_plan: B of 2 GiB or more: multiply from the unpermuted arrays (mispmm_csr_f32)");
     if (rowMap && !row_gather_supports_map(M, K, N, ldc, vec, uniformRowNnz ? uniformRowNnz : nnz / M))
         return fail(MISPMM_ERR_UNSUPPORTED, "csr_plan: the row-mapped kernel takes 16-byte-aligned operands with N a multiple of 32 "
                                             "(per XCD column part), C below 2 GiB and short rows: multiply from the unpermuted arrays");
-    const bool batched_ok = vec == 4 && static_cast<uint64_t>(M) * ldc * 4u <= 0x7FFFFFFFull && (N / xcd_tiling(N, vec, K).q) % 32 == 0 &&
+    const bool batched_ok = vec == 4 && fits_buffer(M, ldc, 4) && (N / xcd_tiling(N, vec, K).q) % 32 == 0 &&
                             !(uniformRowNnz == 0 && nnz / M >= 24);
     auto launch = [&](RowGatherArgs &ga) {
         ga.rowMap = rowMap;
         ga.row_len_guess = uniform_guess(M, nnz);
         row_gather_declined() = false;
         if (uniformRowNnz && try_row_stream(ga, uniformRowNnz, false, acc_mode == MISPMM_ACC_REFERENCE ? 0 : 2, vec, -1)) return true;
-        if (uniformRowNnz) {
-            if (acc_mode == MISPMM_ACC_REFERENCE) launch_row_gather_auto<AccRefWide>(ga, UniformRows{uniformRowNnz}, vec);
-            else launch_row_gather_auto<AccFast>(ga, UniformRows{uniformRowNnz}, vec);
-        } else {
-            if (acc_mode == MISPMM_ACC_REFERENCE) launch_row_gather_auto<AccRefWide>(ga, CsrRows{rowPtrs}, vec);
-            else launch_row_gather_auto<AccFast>(ga, CsrRows{rowPtrs}, vec);
-        }
+        launch_row_gather_auto(acc_mode, ga, uniformRowNnz, rowPtrs, vec);
         return !row_gather_declined();
     };
     const char *declined = "csr_plan: the row-gather body chosen for this shape has no row-mapped form: multiply from the unpermuted arrays";
@@ -898,7 +864,7 @@ extern "C" int mispmm_csr_autotune_plan_f32(mispmm_stream_t stream, uint32_t M, 
     auto run = [&](int which) -> int {
         if (which == 1)
             return mispmm_csr_plan_f32(stream, M, K, nnz, planRowPtrs, planColIdxs, planVals, uniformRowNnz, planRowMap, 1, bl, N, N, cl, N, acc_mode);
-        if (uniformRowNnz && static_cast<uint64_t>(K) * N * 4u <= 0x7FFFFFFFull)
+        if (uniformRowNnz && fits_buffer(K, N, 4))
             return mispmm_csr_uniform_f32(stream, M, K, uniformRowNnz, colIdxs, vals, B, N, N, C, N, acc_mode);
         return mispmm_csr_f32(stream, M, K, nnz, rowPtrs, colIdxs, vals, B, N, N, C, N, MISPMM_KERNEL_AUTO, acc_mode);
     };

@@ -59,23 +59,12 @@ static void launch_ell_wide(const EllArgs &a) {
                        a.ldb, a.C, a.ldc);
 }
 
-template <int VEC, class Acc>
-static void launch_ell_wide_g(const EllArgs &a, int g) {
-    switch (g) {
-        case 8: launch_ell_wide<8, VEC, Acc>(a); break;
-        case 16: launch_ell_wide<16, VEC, Acc>(a); break;
-        case 32: launch_ell_wide<32, VEC, Acc>(a); break;
-        default: launch_ell_wide<64, VEC, Acc>(a); break;
-    }
-}
-
 template <class Acc>
 static void launch_ell_v(const EllArgs &a, int vec) {
-    if (static_cast<uint64_t>(a.K) * a.ldb * 4u > 0x7FFFFFFFull) {  // B too large for 32-bit buffer offsets
-        const int g = pick_group(a.N, vec);
-        if (vec == 4) launch_ell_wide_g<4, Acc>(a, g);
-        else if (vec == 2) launch_ell_wide_g<2, Acc>(a, g);
-        else launch_ell_wide_g<1, Acc>(a, g);
+    if (!fits_buffer(a.K, a.ldb, 4)) {  // B too large for 32-bit buffer offsets
+        with_vec(vec, [&](auto v) {
+            with_group(pick_group(a.N, vec), [&](auto g) { launch_ell_wide<decltype(g)::value, decltype(v)::value, Acc>(a); });
+        });
         return;
     }
     const RowGatherArgs ga{a.stream, a.M, a.K, a.colIdxs, a.vals, a.B, a.N, a.ldb, a.C, a.ldc};
@@ -92,15 +81,13 @@ extern "C" int mispmm_ell_f32(mispmm_stream_t stream, uint32_t M, uint32_t K, ui
                               const float *vals, const float *B, uint32_t N, uint32_t ldb, float *C, uint32_t ldc,
                               int kernel, int acc_mode) {
     if (kernel < 0 || kernel > MISPMM_ELL_NUM_KERNELS) return fail(MISPMM_ERR_INVALID_ARG, "ell: unknown kernel id %d", kernel);
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "ell: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("ell", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
     if (width != 0 && (!colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "ell: colIdxs or vals is null");
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
     const EllArgs a{as_stream(stream), M, K, width, colIdxs, vals, B, N, ldb, C, ldc};
     const int vec = pick_vec(B, ldb, C, ldc, N);
-    if (acc_mode == MISPMM_ACC_REFERENCE) launch_ell_v<AccRefF32>(a, vec);
-    else launch_ell_v<AccFast>(a, vec);
+    with_acc<AccRefF32, AccFast>(acc_mode, [&](auto acc) { launch_ell_v<typename decltype(acc)::type>(a, vec); });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }

@@ -47,29 +47,15 @@ void launch_f64(const F64Args &a, uint32_t q) {
                        a.N, a.ldb, a.rowPtrs, a.colIdxs, a.vals, a.B, b_bytes, a.C, c_bytes, a.ldc);
 }
 
-template <int VEC, class Acc, bool WIDE>
-void launch_f64_g(const F64Args &a, uint32_t q) {
-    switch (pick_group(a.N / q, VEC)) {
-        case 8: launch_f64<8, VEC, Acc, WIDE>(a, q); break;
-        case 16: launch_f64<16, VEC, Acc, WIDE>(a, q); break;
-        case 32: launch_f64<32, VEC, Acc, WIDE>(a, q); break;
-        default: launch_f64<64, VEC, Acc, WIDE>(a, q); break;
-    }
-}
-
 template <class Acc>
 void launch_f64_acc(const F64Args &a) {
     const int vec = pick_vec_f64(a);
     const uint32_t q = f64_parts(a.N, vec);
-    // a raw buffer descriptor spans less than 2 GiB and bit 31 of an offset marks a dropped load
-    const bool wide = static_cast<uint64_t>(a.K) * a.ldb * 8u > 0x7FFFFFFFull || static_cast<uint64_t>(a.M) * a.ldc * 8u > 0x7FFFFFFFull;
-    if (wide) {
-        if (vec == 2) launch_f64_g<2, Acc, true>(a, q);
-        else launch_f64_g<1, Acc, true>(a, q);
-    } else {
-        if (vec == 2) launch_f64_g<2, Acc, false>(a, q);
-        else launch_f64_g<1, Acc, false>(a, q);
-    }
+    with_flag(!fits_buffer(a.K, a.ldb, 8) || !fits_buffer(a.M, a.ldc, 8), [&](auto wide) {
+        with_const<2, 1>(vec, [&](auto v) {
+            with_group(pick_group(a.N / q, vec), [&](auto g) { launch_f64<decltype(g)::value, decltype(v)::value, Acc, decltype(wide)::value>(a, q); });
+        });
+    });
 }
 
 }  // namespace
@@ -81,17 +67,14 @@ using namespace mispmm;
 extern "C" int mispmm_csr_f64(mispmm_stream_t stream, uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs,
                               const uint32_t *colIdxs, const double *vals, const double *B, uint32_t N, uint32_t ldb,
                               double *C, uint32_t ldc, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "csr_f64: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("csr_f64", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
-    if (!rowPtrs) return fail(MISPMM_ERR_INVALID_ARG, "csr_f64: rowPtrs is null");
-    if (nnz != 0 && (!colIdxs || !vals)) return fail(MISPMM_ERR_INVALID_ARG, "csr_f64: colIdxs or vals is null");
+    if (int s = check_row_list("csr_f64", rowPtrs, nnz, colIdxs, vals)) return s;
     if (!B || !C) return fail(MISPMM_ERR_INVALID_ARG, "csr_f64: B or C is null");
     if (ldb < N || ldc < N)
         return fail(MISPMM_ERR_INVALID_ARG, "csr_f64: leading dimension smaller than N (N=%u ldb=%u ldc=%u)", N, ldb, ldc);
     const F64Args a{as_stream(stream), M, K, rowPtrs, colIdxs, vals, B, N, ldb, C, ldc};
-    if (acc_mode == MISPMM_ACC_REFERENCE) launch_f64_acc<Acc64Ref>(a);
-    else launch_f64_acc<Acc64Fast>(a);
+    with_acc<Acc64Ref, Acc64Fast>(acc_mode, [&](auto acc) { launch_f64_acc<typename decltype(acc)::type>(a); });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }

@@ -225,20 +225,18 @@ extern "C" int mispmm_csr_panel_f32(mispmm_stream_t stream, uint32_t M, uint32_t
                                     const uint32_t *colIdxs, const float *vals, const uint32_t *panelPtrs, uint32_t panelRows,
                                     const float *B, uint32_t N, uint32_t ldb, float *C, uint32_t ldc, int acc_mode) {
     (void)rowPtrs;  // panelPtrs holds every row's bounds (its first and last offset): the kernel never reads the row pointers
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "csr_panel: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("csr_panel", acc_mode)) return s;
     if (M == 0 || N == 0) return MISPMM_OK;
     if (!panelPtrs || (nnz != 0 && (!colIdxs || !vals))) return fail(MISPMM_ERR_INVALID_ARG, "csr_panel: null pointer");
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
     if (!panel_rows_supported(panelRows))
         return fail(MISPMM_ERR_UNSUPPORTED, "csr_panel: panels of 64 or 128 B rows (got %u; build them with mispmm_csr_panel_rows())", panelRows);
     const uint64_t offsets = static_cast<uint64_t>(M) * (ceil_div(K, panelRows) + 1u);
-    if (pick_vec(B, ldb, C, ldc, N) != 4 || static_cast<uint64_t>(K) * ldb * 4u > 0x7FFFFFFFull ||
-        static_cast<uint64_t>(M) * ldc * 4u > 0x7FFFFFFFull || static_cast<uint64_t>(nnz) * 4u > 0x7FFFFFFFull || offsets > 0x7FFFFFFFull ||
-        ceil_div(M, 32u) >= (1u << 24))
+    if (pick_vec(B, ldb, C, ldc, N) != 4 || !fits_buffer(K, ldb, 4) || !fits_buffer(M, ldc, 4) || !fits_buffer(nnz, 1, 4) ||
+        !fits_buffer(offsets, 1, 1) || ceil_div(M, 32u) >= (1u << 24))
         return fail(MISPMM_ERR_UNSUPPORTED, "csr_panel: N a multiple of 4 with 16-byte-aligned B, C, ldb, ldc; B, C and the entries below 2 GiB");
     const PanelArgs a{as_stream(stream), M, K, nnz, colIdxs, vals, panelPtrs, B, N, ldb, C, ldc};
-    if (!(acc_mode == MISPMM_ACC_REFERENCE ? launch_panels<AccRefWide>(a, panelRows) : launch_panels<AccFast>(a, panelRows)))
+    if (!with_acc<AccRefWide, AccFast>(acc_mode, [&](auto acc) { return launch_panels<typename decltype(acc)::type>(a, panelRows); }))
         return fail(MISPMM_ERR_UNSUPPORTED, "csr_panel: no kernel is built for this MISPMM_PANEL_P / MISPMM_PANEL_R / MISPMM_PANEL_DMA combination");
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;

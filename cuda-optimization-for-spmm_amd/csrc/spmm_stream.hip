@@ -72,8 +72,8 @@ bool try_row_stream(const RowGatherArgs &a, uint32_t width, bool padded, int acc
     static const int knob = knob_int("MISPMM_STREAM", 0);    // 1: take the persistent launch wherever an instance exists
     if (force < 0) force = knob;
     if (force <= 0 || a.batch != 0 || vec != 4 || width < 9 || width > 16 || a.M == 0) return false;
-    if (static_cast<uint64_t>(a.K) * a.ldb * 4u > 0x7FFFFFFFull || static_cast<uint64_t>(a.M) * a.ldc * 4u > 0x7FFFFFFFull) return false;
-    if (static_cast<uint64_t>(a.M) * width * 4u > 0x7FFFFFFFull) return false;               // (col, val) through buffer descriptors
+    if (!fits_buffer(a.K, a.ldb, 4) || !fits_buffer(a.M, a.ldc, 4)) return false;
+    if (!fits_buffer(a.M, width, 4)) return false;                                           // (col, val) through buffer descriptors
     if (static_cast<uint64_t>(a.M) + 3ull * kCUs * 160u > 0xFFFFFFFFull) return false;       // row + 2 * stride stays in 32 bits
     const XcdTiling t = xcd_tiling(a.N, vec, a.K);
     if (a.N % t.q != 0) return false;

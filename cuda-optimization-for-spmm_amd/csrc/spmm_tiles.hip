@@ -114,20 +114,17 @@ static void launch_tiles(hipStream_t st, uint32_t numTiles, const uint32_t *tile
     // staging through registers (ds_write_b128) or by LDS-DMA: MISPMM_TILE_DMA=0 / 1 in the tuning build (default: DMA, the faster)
     static const bool dma = knob_int("MISPMM_TILE_DMA", 1) != 0;
     note_kernel("csr_lds_tile<%s,%s> xcd %ux%u, %u tiles", acc_tag<Acc>(), dma ? "lds-dma" : "ds_write", 1u << t.log2p, t.q, numTiles);
-#define MISPMM_TILE_LAUNCH(WW, DD)                                                                                                          \
-    hipLaunchKernelGGL((csr_lds_tile_kernel<Acc, WW, DD>), grid, dim3(256), 0, st, tileRowPtrs, tileColPtrs, tileCols, slots, vals, B, b_bytes, \
-                       width, ldb, numTiles, t.log2p | (chunk << 8), cols_per_part, N, rowMap, C, c_bytes, ldc)
-#define MISPMM_TILE_PICK(DD)                     \
-    do {                                         \
-        if (width > 14) MISPMM_TILE_LAUNCH(16, DD);      \
-        else if (width > 12) MISPMM_TILE_LAUNCH(14, DD); \
-        else if (width > 8) MISPMM_TILE_LAUNCH(12, DD);  \
-        else MISPMM_TILE_LAUNCH(8, DD);                  \
-    } while (0)
-    if (dma) MISPMM_TILE_PICK(true);
-    else MISPMM_TILE_PICK(false);
-#undef MISPMM_TILE_PICK
-#undef MISPMM_TILE_LAUNCH
+    auto launch = [&](auto d) {
+        // the kernel's unrolled row width: the smallest of 16, 14, 12, 8 that holds the rows
+        with_const<16, 14, 12, 8>(width > 14 ? 16 : width > 12 ? 14 : width > 8 ? 12 : 8, [&](auto w) {
+            hipLaunchKernelGGL((csr_lds_tile_kernel<Acc, decltype(w)::value, decltype(d)::value>), grid, dim3(256), 0, st, tileRowPtrs, tileColPtrs,
+                               tileCols, slots, vals, B, b_bytes, width, ldb, numTiles, t.log2p | (chunk << 8), cols_per_part, N, rowMap, C, c_bytes,
+                               ldc);
+        });
+    };
+    // a plain `if` on the knob: the production build folds it where it stands and holds no host stub of the other form
+    if (dma) launch(std::true_type{});
+    else launch(std::false_type{});
 }
 
 }  // namespace mispmm
@@ -138,8 +135,7 @@ extern "C" int mispmm_csr_lds_tile_f32(mispmm_stream_t stream, uint32_t M, uint3
                                        const uint32_t *tileRowPtrs, const uint32_t *tileColPtrs, const uint32_t *tileCols, const uint8_t *slots,
                                        const float *vals, const uint32_t *rowMap, const float *B, uint32_t N, uint32_t ldb, float *C,
                                        uint32_t ldc, int acc_mode) {
-    if (acc_mode != MISPMM_ACC_REFERENCE && acc_mode != MISPMM_ACC_FAST)
-        return fail(MISPMM_ERR_INVALID_ARG, "csr_lds_tile: unknown accumulate mode %d", acc_mode);
+    if (int s = check_acc_mode("csr_lds_tile", acc_mode)) return s;
     if (M == 0 || N == 0 || numTiles == 0) return MISPMM_OK;
     if (!tileRowPtrs || !tileColPtrs || !tileCols || !slots || !vals || !rowMap) return fail(MISPMM_ERR_INVALID_ARG, "csr_lds_tile: null pointer");
     if (int s = check_dense_args(B, N, ldb, C, ldc)) return s;
@@ -148,13 +144,13 @@ extern "C" int mispmm_csr_lds_tile_f32(mispmm_stream_t stream, uint32_t M, uint3
     if (maxTileCols > kTileCols)
         return fail(MISPMM_ERR_UNSUPPORTED, "csr_lds_tile: a tile lists %u columns, the LDS image holds %u", maxTileCols, kTileCols);
     const XcdTiling t = xcd_tiling(N, pick_vec(B, ldb, C, ldc, N), K);
-    if (pick_vec(B, ldb, C, ldc, N) != 4 || N % t.q != 0 || (N / t.q) % 64 != 0 || static_cast<uint64_t>(K) * ldb * 4u > 0x7FFFFFFFull ||
-        static_cast<uint64_t>(M) * ldc * 4u > 0x7FFFFFFFull || static_cast<uint64_t>(ceil_div(numTiles, 1u << t.log2p)) >= (1u << 24))
+    if (pick_vec(B, ldb, C, ldc, N) != 4 || N % t.q != 0 || (N / t.q) % 64 != 0 || !fits_buffer(K, ldb, 4) || !fits_buffer(M, ldc, 4) ||
+        static_cast<uint64_t>(ceil_div(numTiles, 1u << t.log2p)) >= (1u << 24))
         return fail(MISPMM_ERR_UNSUPPORTED, "csr_lds_tile: 16-byte-aligned operands, column parts of whole 64-column groups, B and C below 2 GiB");
-    if (acc_mode == MISPMM_ACC_REFERENCE)
-        launch_tiles<AccRefWide>(as_stream(stream), numTiles, tileRowPtrs, tileColPtrs, tileCols, slots, vals, rowMap, rowNnz, K, B, N, ldb, C, M, ldc);
-    else
-        launch_tiles<AccFast>(as_stream(stream), numTiles, tileRowPtrs, tileColPtrs, tileCols, slots, vals, rowMap, rowNnz, K, B, N, ldb, C, M, ldc);
+    with_acc<AccRefWide, AccFast>(acc_mode, [&](auto acc) {
+        launch_tiles<typename decltype(acc)::type>(as_stream(stream), numTiles, tileRowPtrs, tileColPtrs, tileCols, slots, vals, rowMap, rowNnz, K, B, N,
+                                                   ldb, C, M, ldc);
+    });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }
