@@ -312,24 +312,61 @@ class _BlockSparseAttention(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         q, k, v, p = ctx.saved_tensors
-        a = ctx.a
-        grad_out = grad_out.contiguous()           # e.g. out.sum().backward() hands in an expanded scalar, strides (0, 0)
-        g = ops.f32_to_bf16(grad_out) if grad_out.dtype == torch.float32 else _bits(grad_out)
-        transposed = lambda blocks: blocks[a.perm].transpose(1, 2).contiguous()   # noqa: E731  A's blocks as A^T's
-        grad_q = grad_k = grad_v = None
-        if ctx.needs_input_grad[2]:
-            grad_v = ops.spmm_bsr_bf16(a.tpattern, transposed(p), g, out_bf16=True).view(torch.bfloat16)
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            dp = ops.sddmm_bsr_bf16(a.fwd, g, _bits(v))
-            ds = ops.softmax_bsr_bwd(a.fwd, p, dp, scale=ctx.scale, out_bf16=True)
-            if ctx.needs_input_grad[0]:
-                grad_q = ops.spmm_bsr_bf16(a.fwd, ds, _bits(k), out_bf16=True).view(torch.bfloat16)
-            if ctx.needs_input_grad[1]:
-                grad_k = ops.spmm_bsr_bf16(a.tpattern, transposed(ds), _bits(q), out_bf16=True).view(torch.bfloat16)
-        return grad_q, grad_k, grad_v, None, None, None, None
+        return (*_attention_grads(ctx.a, q, k, v, p, grad_out, ctx.scale, ctx.needs_input_grad), None, None, None, None)
 
 
-def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.float32):
+def _attention_grads(a, q, k, v, p, grad_out, scale, needs):
+    """(grad_q, grad_k, grad_v) of one head, bfloat16 or None where `needs` says so: the gradient chain block_sparse_attention
+    documents, on the bf16 weights p ([num_blocks, bS, bS] int16 bits)."""
+    grad_out = grad_out.contiguous()           # e.g. out.sum().backward() hands in an expanded scalar, strides (0, 0)
+    g = ops.f32_to_bf16(grad_out) if grad_out.dtype == torch.float32 else _bits(grad_out)
+    transposed = lambda blocks: blocks[a.perm].transpose(1, 2).contiguous()   # noqa: E731  A's blocks as A^T's
+    grad_q = grad_k = grad_v = None
+    if needs[2]:
+        grad_v = ops.spmm_bsr_bf16(a.tpattern, transposed(p), g, out_bf16=True).view(torch.bfloat16)
+    if needs[0] or needs[1]:
+        dp = ops.sddmm_bsr_bf16(a.fwd, g, _bits(v))
+        ds = ops.softmax_bsr_bwd(a.fwd, p, dp, scale=scale, out_bf16=True)
+        if needs[0]:
+            grad_q = ops.spmm_bsr_bf16(a.fwd, ds, _bits(k), out_bf16=True).view(torch.bfloat16)
+        if needs[1]:
+            grad_k = ops.spmm_bsr_bf16(a.tpattern, transposed(ds), _bits(q), out_bf16=True).view(torch.bfloat16)
+    return grad_q, grad_k, grad_v
+
+
+class _FusedBlockSparseAttention(torch.autograd.Function):
+    """The forward in one launch for all heads (ops.attention_bsr_bf16).  q, k, v are saved and the weights are not: the
+    backward recomputes S and P head by head with the kernels of the three-launch forward -- to the bits that forward would
+    have saved -- and runs its gradient chain."""
+    @staticmethod
+    def forward(ctx, q, k, v, a, scale, mask, out_bf16):
+        q, k, v = q.detach(), k.detach(), v.detach()
+        out = ops.attention_bsr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, mask=mask, out_bf16=out_bf16)
+        ctx.a, ctx.scale, ctx.mask = a, scale, mask
+        ctx.save_for_backward(q, k, v)
+        return out.view(torch.bfloat16) if out_bf16 else out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v = ctx.saved_tensors
+        a, needs = ctx.a, ctx.needs_input_grad
+        if not any(needs[:3]):
+            return (None,) * 7
+        heads = [None] if q.dim() == 2 else range(q.shape[0])
+        grads = ([], [], [])
+        for h in heads:
+            qh, kh, vh, gh = (t if h is None else t[h] for t in (q, k, v, grad_out))
+            qh, kh, vh = qh.contiguous(), kh.contiguous(), vh.contiguous()
+            s = ops.sddmm_bsr_bf16(a.fwd, _bits(qh), _bits(kh))
+            p = ops.softmax_bsr(a.fwd, s, scale=ctx.scale, mask=ctx.mask, out_bf16=True)
+            for held, grad in zip(grads, _attention_grads(a, qh, kh, vh, p, gh, ctx.scale, needs)):
+                held.append(grad)
+        merged = [None if held[0] is None else (held[0] if q.dim() == 2 else torch.stack(held)) for held in grads]
+        return (*merged, None, None, None, None)
+
+
+def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.float32, fused=False):
     """Attention on A's block pattern in bf16: matrix row r attends to the columns of the blocks A stores in r's block row.
 
         S = ops.sddmm_bsr_bf16(q, k)                               # fp32 [num_blocks, bS, bS]: <q_r, k_c>, fp32 accumulation
@@ -347,9 +384,17 @@ def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.fl
     transpose's permutation; dP = ops.sddmm_bsr_bf16(grad_out, v) in fp32; dS = ops.softmax_bsr_bwd(P, dP, scale) rounded to
     bf16 once; dQ = ops.spmm_bsr_bf16(dS, k); dK = ops.spmm_bsr_bf16 on A^T's pattern with dS's blocks gathered likewise and q.
     The three gradients are fp32 sums rounded once and returned as bfloat16.  Each gradient, and each kernel behind it, runs
-    only if its input requires it.  A block row of A without blocks gives zero rows."""
+    only if its input requires it.  A block row of A without blocks gives zero rows.
+    fused=True: the forward is ONE launch for all heads (ops.attention_bsr_bf16: online softmax, neither S nor P written);
+    q, k, v may then be [H, M, D] / [H, K, D] / [H, K, Dv] with any head and row strides (last dimension contiguous) and out
+    is [H, M, Dv]; D and Dv multiples of 8 up to 128.  out differs from the unfused result by roundings (the weights are
+    normalised by the sum of their bf16 values) and is held to the same tolerance.  q, k, v are saved and P is not: the
+    backward recomputes S and P per head with ops.sddmm_bsr_bf16 / ops.softmax_bsr and runs the chain above unchanged, so the
+    gradients are the unfused path's, bit for bit.  fused=False is the three-launch path, unchanged."""
     ops._require_gpu(a.fwd.block_row_ptrs, q, k, v, mask)
     out_bf16 = _check_out_dtype(out_dtype)
+    if fused:
+        return _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16)
     for t, rows, what in ((q, a.fwd.num_rows, "q"), (k, a.fwd.num_cols, "k"), (v, a.fwd.num_cols, "v")):
         if t.dtype != torch.bfloat16:
             raise ValueError(f"{what} must be torch.bfloat16")
@@ -367,3 +412,27 @@ def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.fl
     if scale is None:
         scale = q.shape[1] ** -0.5
     return _BlockSparseAttention.apply(q, k, v, a, float(scale), mask, out_bf16)
+
+
+def _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16):
+    dims = {t.dim() for t in (q, k, v)}
+    if dims not in ({2}, {3}):
+        raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    for t, rows, what in ((q, a.fwd.num_rows, "q"), (k, a.fwd.num_cols, "k"), (v, a.fwd.num_cols, "v")):
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"{what} must be torch.bfloat16")
+        if t.shape[-2] != rows or t.shape[:-2] != q.shape[:-2]:
+            raise ValueError(f"{what} must be [{rows}, N] or [H, {rows}, N] with q's H, not {tuple(t.shape)}")
+        if t.shape[-1] == 0 or t.shape[-1] % 8 != 0 or t.shape[-1] > ops.ATTN_MAX_WIDTH:
+            raise ValueError(f"the fused attention kernel takes widths in multiples of 8 up to {ops.ATTN_MAX_WIDTH}: {what} has "
+                             f"{t.shape[-1]} columns")
+        if t.stride(-1) != 1:
+            raise ValueError(f"{what} must have a contiguous last dimension")
+    if q.shape[-1] != k.shape[-1]:
+        raise ValueError(f"q and k must have the same number of columns, not {q.shape[-1]} and {k.shape[-1]}")
+    if mask is not None:
+        _check_block_array(a, mask, "mask")
+        mask = mask.detach().contiguous()
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    return _FusedBlockSparseAttention.apply(q, k, v, a, float(scale), mask, out_bf16)

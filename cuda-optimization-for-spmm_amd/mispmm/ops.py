@@ -880,6 +880,79 @@ def softmax_bsr_bwd(a, p, dp, scale=1.0, out_bf16=False, out=None, stream=None):
     return out
 
 
+ATTN_MAX_WIDTH = 128     # D and Dv of the fused attention kernel: multiples of 8 up to this (mispmm_attn.h)
+
+
+def _attn_operand(t, rows, heads, what):
+    """(t as [H, rows, width], row stride, head stride) of a bf16-bits operand given as [rows, width] or [H, rows, width]."""
+    if t.dtype != torch.int16 or t.dim() not in (2, 3):
+        raise ValueError(f"{what} must be an int16 tensor of bf16 bits, [{rows}, width] or [H, {rows}, width], not {t.dtype} {tuple(t.shape)}")
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.shape[1] != rows or (heads is not None and t.shape[0] != heads):
+        raise ValueError(f"{what} must be [{rows}, width] or [{'H' if heads is None else heads}, {rows}, width], not {tuple(t.shape)}")
+    if t.shape[2] > 1 and t.stride(2) != 1:
+        raise ValueError(f"{what} must have a contiguous last dimension")
+    width = t.shape[2]
+    ld = t.stride(1) if rows > 1 else max(width, t.stride(1))
+    if ld < width or any(s < 0 for s in t.stride()):
+        raise ValueError(f"{what} must not overlap its own rows (row stride {ld} < {width} columns), e.g. an expanded tensor")
+    return t, ld, (t.stride(0) if t.shape[0] > 1 else 0)
+
+
+def attention_bsr_bf16(a, q, k, v, scale=None, mask=None, out_bf16=False, return_lse=False, out=None, lse=None, stream=None):
+    """Fused block-sparse attention forward (mispmm_attn_bsr_bf16, libmispmm_attn.so): for every head, out = softmax over each
+    matrix row of (scale * q k^T + mask) on A's stored blocks, times v -- one launch for all heads, the scores and the weights
+    never written.  a: DeviceBSR [M x K] of 16 x 16 or 32 x 32 blocks (index arrays used); q: [M, D], k: [K, D], v: [K, Dv]
+    int16 tensors of bf16 bits, or [H, ...] with any head and row strides whose last dimension is contiguous (e.g. a permuted
+    [M, H, D]); D and Dv multiples of 8 up to 128.  scale defaults to D ** -0.5; mask: float32 [num_blocks, bS, bS], added to
+    the scaled scores, -Inf = masked, shared by the heads.  Returns out, [M, Dv] or [H, M, Dv], float32 or int16 bf16 bits
+    with out_bf16; with return_lse (out, lse), lse the float32 [M] or [H, M] log-sum-exp of each row.  out= and lse= take
+    the results where given: out of the result's shape with a contiguous last dimension, lse contiguous."""
+    from . import capi_attn
+    _require_gpu(a.block_row_ptrs, q, k, v, mask, out, lse)
+    _square_blocks(a)
+    bs = a.block_row_size
+    if q.dim() != k.dim() or q.dim() != v.dim():
+        raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    batched = q.dim() == 3
+    q3, ldq, q_head = _attn_operand(q, a.num_rows, None, "q")
+    heads = q3.shape[0]
+    k3, ldk, k_head = _attn_operand(k, a.num_cols, heads, "k")
+    v3, ldv, v_head = _attn_operand(v, a.num_cols, heads, "v")
+    d, dv = q3.shape[2], v3.shape[2]
+    if k3.shape[2] != d:
+        raise ValueError(f"q and k must have the same number of columns, not {d} and {k3.shape[2]}")
+    for width, what in ((d, "D"), (dv, "Dv")):
+        if width == 0 or width % 8 != 0 or width > ATTN_MAX_WIDTH:
+            raise ValueError(f"the fused attention kernel takes {what} in multiples of 8 up to {ATTN_MAX_WIDTH}, not {width}")
+    if mask is not None:
+        _block_array(a, mask, (torch.float32,), "mask")
+    if scale is None:
+        scale = d ** -0.5
+    dtype = torch.int16 if out_bf16 else torch.float32
+    shape = (heads, a.num_rows, dv)
+    if out is None:
+        out3 = torch.empty(shape, dtype=dtype, device=q.device)
+    else:
+        out3 = out if batched else out.unsqueeze(0)
+        if out.dtype != dtype or tuple(out3.shape) != shape or (dv > 1 and out3.stride(2) != 1) or out3.stride(1) < dv:
+            raise ValueError(f"out must be a {dtype} tensor of shape {shape if batched else shape[1:]} with a contiguous last dimension")
+    want_lse = return_lse or lse is not None
+    if lse is None and want_lse:
+        lse = torch.empty((heads, a.num_rows) if batched else (a.num_rows,), dtype=torch.float32, device=q.device)
+    if lse is not None and (lse.dtype != torch.float32 or tuple(lse.shape) != ((heads, a.num_rows) if batched else (a.num_rows,))
+                            or not lse.is_contiguous()):
+        raise ValueError(f"lse must be a contiguous float32 tensor of shape {(heads, a.num_rows) if batched else (a.num_rows,)}")
+    o_head = out3.stride(0) if heads > 1 else 0
+    capi_attn.check(capi_attn.lib().mispmm_attn_bsr_bf16(
+        _stream_ptr(stream), heads, a.num_rows // bs, a.num_cols, bs, a.num_blocks, _p(a.block_row_ptrs), _p(a.block_col_idxs),
+        _p(q3), ldq, q_head, _p(k3), ldk, k_head, _p(v3), ldv, v_head, d, dv, _p(mask), float(scale), _p(out3), out3.stride(1), o_head,
+        int(bool(out_bf16)), _p(lse)))
+    result = out if out is not None else (out3 if batched else out3[0])
+    return (result, lse) if return_lse else result
+
+
 def bsr_transpose(bsr):
     """(formats.BSR of A^T, perm) on the host: mispmm_csr_transpose_host on the block arrays, a stable counting sort of A's
     blocks by block column.  Block t of A^T is block perm[t] of A with its two inner axes swapped; a block row of A^T lists its
