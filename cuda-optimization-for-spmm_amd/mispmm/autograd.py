@@ -189,6 +189,14 @@ class TrainableBSR:
     perm: torch.Tensor          # int64, device: block t of A^T is block perm[t] of A, its inner axes swapped
     blocks: torch.Tensor        # bfloat16 [num_blocks, bS, bS]: bsr.data rounded to nearest even, for the caller to wrap as a parameter
 
+    _perm32: tuple = dataclasses.field(default=None, repr=False, compare=False)   # (perm it was made from, its int32 copy)
+
+    def perm32(self):
+        """perm as the int32 array the fused attention backward reads: converted once per perm tensor, then kept."""
+        if self._perm32 is None or self._perm32[0] is not self.perm:
+            self._perm32 = (self.perm, self.perm.to(torch.int32).contiguous())
+        return self._perm32[1]
+
     @staticmethod
     def from_host(bsr, device="cuda"):
         if bsr.block_row_size != bsr.block_col_size or bsr.block_row_size not in (16, 32):
@@ -339,20 +347,31 @@ class _FusedBlockSparseAttention(torch.autograd.Function):
     backward recomputes S and P head by head with the kernels of the three-launch forward -- to the bits that forward would
     have saved -- and runs its gradient chain."""
     @staticmethod
-    def forward(ctx, q, k, v, a, scale, mask, out_bf16):
+    def forward(ctx, q, k, v, a, scale, mask, out_bf16, fused_backward=False):
         q, k, v = q.detach(), k.detach(), v.detach()
+        ctx.a, ctx.scale, ctx.mask, ctx.fused_backward = a, scale, mask, fused_backward
+        if fused_backward:                     # the backward kernels read the forward's out and its log-sum-exp
+            out, lse = ops.attention_bsr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, mask=mask, out_bf16=out_bf16, return_lse=True)
+            ctx.save_for_backward(q, k, v, out, lse)
+            return out.view(torch.bfloat16) if out_bf16 else out
         out = ops.attention_bsr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, mask=mask, out_bf16=out_bf16)
-        ctx.a, ctx.scale, ctx.mask = a, scale, mask
         ctx.save_for_backward(q, k, v)
         return out.view(torch.bfloat16) if out_bf16 else out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        q, k, v = ctx.saved_tensors
         a, needs = ctx.a, ctx.needs_input_grad
         if not any(needs[:3]):
-            return (None,) * 7
+            return (None,) * 8
+        if ctx.fused_backward:
+            q, k, v, out, lse = ctx.saved_tensors
+            grad_out = grad_out.contiguous()       # e.g. out.sum().backward() hands in an expanded scalar
+            g = ops.f32_to_bf16(grad_out) if grad_out.dtype == torch.float32 else _bits(grad_out)
+            grads = ops.attention_bsr_bwd_bf16(a.fwd, a.tpattern, a.perm32(), _bits(q), _bits(k), _bits(v), out, lse, g, scale=ctx.scale,
+                                               mask=ctx.mask, grads_bf16=True, need=tuple(needs[:3]))
+            return (*(None if x is None else x.view(torch.bfloat16) for x in grads), None, None, None, None, None)
+        q, k, v = ctx.saved_tensors
         heads = [None] if q.dim() == 2 else range(q.shape[0])
         grads = ([], [], [])
         for h in heads:
@@ -363,10 +382,10 @@ class _FusedBlockSparseAttention(torch.autograd.Function):
             for held, grad in zip(grads, _attention_grads(a, qh, kh, vh, p, gh, ctx.scale, needs)):
                 held.append(grad)
         merged = [None if held[0] is None else (held[0] if q.dim() == 2 else torch.stack(held)) for held in grads]
-        return (*merged, None, None, None, None)
+        return (*merged, None, None, None, None, None)
 
 
-def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.float32, fused=False):
+def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.float32, fused=False, fused_backward=False):
     """Attention on A's block pattern in bf16: matrix row r attends to the columns of the blocks A stores in r's block row.
 
         S = ops.sddmm_bsr_bf16(q, k)                               # fp32 [num_blocks, bS, bS]: <q_r, k_c>, fp32 accumulation
@@ -390,11 +409,19 @@ def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.fl
     is [H, M, Dv]; D and Dv multiples of 8 up to 128.  out differs from the unfused result by roundings (the weights are
     normalised by the sum of their bf16 values) and is held to the same tolerance.  q, k, v are saved and P is not: the
     backward recomputes S and P per head with ops.sddmm_bsr_bf16 / ops.softmax_bsr and runs the chain above unchanged, so the
-    gradients are the unfused path's, bit for bit.  fused=False is the three-launch path, unchanged."""
+    gradients are the unfused path's, bit for bit.  fused=False is the three-launch path, unchanged.
+    fused_backward=True (only with fused=True; off by default): the forward also keeps its per-row log-sum-exp and saves q, k,
+    v, out and lse; the backward makes grad_out contiguous, rounds a float32 grad_out to bf16 as above and is ONE
+    ops.attention_bsr_bwd_bf16 call for all heads -- at most two launches, S, P, dP and dS never written -- asking only for the
+    gradients autograd needs.  The gradients are bfloat16; they differ from the chain's by roundings (P is recomputed as
+    exp(z - lse) in fp32 and dS uses delta = <grad_out, out> in place of <P, dP>) and are held to the derived tolerance of
+    include/mispmm_attn_bwd.h."""
     ops._require_gpu(a.fwd.block_row_ptrs, q, k, v, mask)
     out_bf16 = _check_out_dtype(out_dtype)
+    if fused_backward and not fused:
+        raise ValueError("fused_backward=True is the backward of the fused forward: it needs fused=True")
     if fused:
-        return _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16)
+        return _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16, bool(fused_backward))
     for t, rows, what in ((q, a.fwd.num_rows, "q"), (k, a.fwd.num_cols, "k"), (v, a.fwd.num_cols, "v")):
         if t.dtype != torch.bfloat16:
             raise ValueError(f"{what} must be torch.bfloat16")
@@ -414,7 +441,7 @@ def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.fl
     return _BlockSparseAttention.apply(q, k, v, a, float(scale), mask, out_bf16)
 
 
-def _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16):
+def _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16, fused_backward=False):
     dims = {t.dim() for t in (q, k, v)}
     if dims not in ({2}, {3}):
         raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
@@ -435,4 +462,4 @@ def _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16):
         mask = mask.detach().contiguous()
     if scale is None:
         scale = q.shape[-1] ** -0.5
-    return _FusedBlockSparseAttention.apply(q, k, v, a, float(scale), mask, out_bf16)
+    return _FusedBlockSparseAttention.apply(q, k, v, a, float(scale), mask, out_bf16, fused_backward)

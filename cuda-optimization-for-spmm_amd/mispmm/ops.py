@@ -953,6 +953,95 @@ def attention_bsr_bf16(a, q, k, v, scale=None, mask=None, out_bf16=False, return
     return (result, lse) if return_lse else result
 
 
+def _attn_result(t, shape, batched, bf16, what):
+    """(t as [H, rows, width], row stride, head stride) of a float32 / bf16-bits tensor the backward reads or writes."""
+    dtype = torch.int16 if bf16 else torch.float32
+    t3 = t if batched else t.unsqueeze(0)
+    if t.dtype != dtype or t.dim() != (3 if batched else 2) or tuple(t3.shape) != shape or (shape[2] > 1 and t3.stride(2) != 1) \
+            or (shape[1] > 1 and t3.stride(1) < shape[2]):
+        raise ValueError(f"{what} must be a {dtype} tensor of shape {shape if batched else shape[1:]} with a contiguous last dimension, "
+                         f"not {t.dtype} {tuple(t.shape)} with strides {tuple(t.stride())}")
+    return t3, (t3.stride(1) if shape[1] > 1 else max(shape[2], t3.stride(1))), (t3.stride(0) if shape[0] > 1 else 0)
+
+
+def attention_bsr_bwd_bf16(a, at, perm, q, k, v, out, lse, grad_out, scale=None, mask=None, grads_bf16=True, need=(True, True, True),
+                           dq=None, dk=None, dv=None, delta=None, stream=None):
+    """Fused backward of attention_bsr_bf16 (mispmm_attn_bsr_bwd_bf16, libmispmm_attn_bwd.so): (dq, dk, dv) for every head in
+    at most two launches, the scores, the weights and their gradients never written.  a: the forward's DeviceBSR; at, perm:
+    A^T's pattern and the permutation of its blocks (bsr_transpose; TrainableBSR.tpattern / .perm), perm an integer device
+    tensor (int64 is converted to 32 bits here: hand in int32 to avoid the copy), read only with a mask.  q, k, v: as in the
+    forward; out, lse: what the forward returned (out float32 or int16 bf16 bits, lse float32 contiguous); grad_out: int16
+    bf16 bits of out's shape.  2-D or [H, ...] operands with any strides whose last dimension is contiguous.  need: which of
+    (dq, dk, dv) to compute; the others come back None and their work is skipped.  The gradients are int16 bf16 bits
+    (grads_bf16, the fp32 sums rounded once) or float32; dq= / dk= / dv= take them where given.  delta: a contiguous float32
+    workspace of lse's shape, allocated here unless given."""
+    from . import capi_attn_bwd
+    _require_gpu(a.block_row_ptrs, at.block_row_ptrs, perm, q, k, v, out, lse, grad_out, mask, dq, dk, dv, delta)
+    _square_blocks(a)
+    bs = a.block_row_size
+    if (at.block_row_size, at.block_col_size, at.num_rows, at.num_cols, at.num_blocks) != (bs, bs, a.num_cols, a.num_rows, a.num_blocks):
+        raise ValueError(f"at must be the pattern of A^T: {a.num_cols} x {a.num_rows} of {a.num_blocks} {bs} x {bs} blocks")
+    if len({q.dim(), k.dim(), v.dim(), out.dim(), grad_out.dim()}) != 1:
+        raise ValueError("q, k, v, out and grad_out must all be 2-D or all [H, ...]")
+    batched = q.dim() == 3
+    q3, ldq, q_head = _attn_operand(q, a.num_rows, None, "q")
+    heads = q3.shape[0]
+    k3, ldk, k_head = _attn_operand(k, a.num_cols, heads, "k")
+    v3, ldv, v_head = _attn_operand(v, a.num_cols, heads, "v")
+    g3, ldg, g_head = _attn_operand(grad_out, a.num_rows, heads, "grad_out")
+    d, dvw = q3.shape[2], v3.shape[2]
+    if k3.shape[2] != d:
+        raise ValueError(f"q and k must have the same number of columns, not {d} and {k3.shape[2]}")
+    if g3.shape[2] != dvw:
+        raise ValueError(f"grad_out must have v's {dvw} columns, not {g3.shape[2]}")
+    for width, what in ((d, "D"), (dvw, "Dv")):
+        if width == 0 or width % 8 != 0 or width > ATTN_MAX_WIDTH:
+            raise ValueError(f"the fused attention kernel takes {what} in multiples of 8 up to {ATTN_MAX_WIDTH}, not {width}")
+    if out.dtype not in (torch.float32, torch.int16):
+        raise ValueError(f"out must be the forward's result, float32 or int16 bf16 bits, not {out.dtype}")
+    out_bf16 = out.dtype == torch.int16
+    o3, ldo, o_head = _attn_result(out, (heads, a.num_rows, dvw), batched, out_bf16, "out")
+    rows_shape = (heads, a.num_rows) if batched else (a.num_rows,)
+    if lse.dtype != torch.float32 or tuple(lse.shape) != rows_shape or not lse.is_contiguous():
+        raise ValueError(f"lse must be a contiguous float32 tensor of shape {rows_shape}")
+    if mask is not None:
+        _block_array(a, mask, (torch.float32,), "mask")
+    if len(need) != 3:
+        raise ValueError("need holds three flags: (dq, dk, dv)")
+    if perm is not None:
+        if perm.dtype not in (torch.int32, torch.int64) or perm.numel() != a.num_blocks:
+            raise ValueError(f"perm must hold {a.num_blocks} int32 or int64 block numbers")
+        if perm.dtype == torch.int64:
+            perm = perm.to(torch.int32)
+        perm = perm.contiguous()
+    elif mask is not None and (need[1] or need[2]):
+        raise ValueError("with a mask, dk and dv need perm")
+    if scale is None:
+        scale = d ** -0.5
+    grads = []
+    for wanted, given, rows, width, what in ((need[0], dq, a.num_rows, d, "dq"), (need[1], dk, a.num_cols, d, "dk"), (need[2], dv, a.num_cols, dvw, "dv")):
+        if not wanted:
+            grads.append((None, None, 0, 0))
+            continue
+        shape = (heads, rows, width)
+        if given is None:
+            given = torch.empty(shape if batched else shape[1:], dtype=torch.int16 if grads_bf16 else torch.float32, device=q.device)
+        t3, ld, head = _attn_result(given, shape, batched, grads_bf16, what)
+        grads.append((given, t3, ld, head))
+    if need[0] or need[1]:
+        if delta is None:
+            delta = torch.empty(rows_shape, dtype=torch.float32, device=q.device)
+        elif delta.dtype != torch.float32 or tuple(delta.shape) != rows_shape or not delta.is_contiguous():
+            raise ValueError(f"delta must be a contiguous float32 tensor of shape {rows_shape}")
+    (rq, q_out, lddq, dq_head), (rk, k_out, lddk, dk_head), (rv, v_out, lddv, dv_head) = grads
+    capi_attn_bwd.check(capi_attn_bwd.lib().mispmm_attn_bsr_bwd_bf16(
+        _stream_ptr(stream), heads, a.num_rows // bs, a.num_cols, bs, a.num_blocks, _p(a.block_row_ptrs), _p(a.block_col_idxs),
+        _p(at.block_row_ptrs), _p(at.block_col_idxs), _p(perm), _p(q3), ldq, q_head, _p(k3), ldk, k_head, _p(v3), ldv, v_head,
+        _p(g3), ldg, g_head, _p(o3), ldo, o_head, int(out_bf16), _p(lse), _p(delta), d, dvw, _p(mask), float(scale),
+        _p(q_out), lddq, dq_head, _p(k_out), lddk, dk_head, _p(v_out), lddv, dv_head, int(bool(grads_bf16))))
+    return rq, rk, rv
+
+
 def bsr_transpose(bsr):
     """(formats.BSR of A^T, perm) on the host: mispmm_csr_transpose_host on the block arrays, a stable counting sort of A's
     blocks by block column.  Block t of A^T is block perm[t] of A with its two inner axes swapped; a block row of A^T lists its
