@@ -24,7 +24,13 @@ Every step and every gradient is a library kernel; a mask is a -Inf score.  The 
     c = spmm_bsr(a, w, b)                              # forward: ops.spmm_bsr_bf16 (MFMA), b bfloat16
     c.sum().backward()                                 # w.grad: ops.sddmm_bsr_bf16; b.grad: ops.spmm_bsr_bf16 on A^T's pattern
 
-Both gradients come back in bfloat16.  Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, a fused
+Both gradients come back in bfloat16.  The CSR product with fp32 values and the activations in bfloat16:
+
+    a = TrainableCSR.from_host(csr)                    # float32
+    c = spmm_bf16(a, w, b)                             # forward: ops.spmm_csr_bf16, b bfloat16, c bfloat16 or float32
+    c.sum().backward()                                 # b.grad (bfloat16): the same kernel on A^T; w.grad: ops.sddmm_csr, widened
+
+Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, a fused
 SDDMM + softmax, the column-compacted block layouts (their tiles are built on the host from the values), a device kernel for
 the blocks[perm] transpose."""
 import dataclasses
@@ -463,3 +469,53 @@ def _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16, fused_backw
     if scale is None:
         scale = q.shape[-1] ** -0.5
     return _FusedBlockSparseAttention.apply(q, k, v, a, float(scale), mask, out_bf16, fused_backward)
+
+
+# ---- the CSR product with B in bf16 (ops.spmm_csr_bf16): fp32 values, bf16 activations
+class _SpmmCsrBf16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, b, a, out_bf16, acc):
+        ctx.a, ctx.acc = a, acc
+        ctx.save_for_backward(values, b)
+        c = ops.spmm_csr_bf16(dataclasses.replace(a.fwd, data=values.detach().contiguous()), _bits(b.detach()), out_bf16=out_bf16, acc=acc)
+        return c.view(torch.bfloat16) if out_bf16 else c
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_c):
+        values, b = ctx.saved_tensors
+        a = ctx.a
+        grad_c = grad_c.contiguous()           # e.g. C.sum().backward() hands in an expanded scalar, strides (0, 0)
+        g = ops.f32_to_bf16(grad_c) if grad_c.dtype == torch.float32 else _bits(grad_c)
+        grad_values = grad_b = None
+        if ctx.needs_input_grad[0]:
+            grad_values = ops.sddmm_csr(a.fwd, ops.bf16_to_f32(g), ops.bf16_to_f32(_bits(b)), acc=ctx.acc)
+        if ctx.needs_input_grad[1]:
+            t = dataclasses.replace(a.tpattern, data=values.detach()[a.perm])
+            grad_b = ops.spmm_csr_bf16(t, g, out_bf16=True, acc=ctx.acc).view(torch.bfloat16)
+        return grad_values, grad_b, None, None, None
+
+
+def spmm_bf16(a, values, b, out_dtype=torch.bfloat16, acc="fast"):
+    """C = A @ B with the activations in bfloat16, differentiable in `values` (float32, A's entries in storage order) and in
+    `b` ([K, N] bfloat16, unit column stride, any row stride).  a: a float32 TrainableCSR; out_dtype: torch.bfloat16 or
+    torch.float32.  The forward is ops.spmm_csr_bf16, bit for bit (acc="reference": the CSR rule, a double sum).  The
+    backward makes grad_C contiguous and, where C is float32, rounds it to bfloat16 (to nearest even) once, as spmm_bsr does.
+    grad_b is the same kernel on A^T's pattern with values[a.perm] and comes back in bfloat16; grad_values is ops.sddmm_csr
+    on grad_C and b widened to float32 (exact), in float32.  A gradient is computed only for the inputs that require one.
+    Not built: an SDDMM on a CSR pattern that reads bf16 itself."""
+    ops._require_gpu(a.fwd.row_ptrs, values, b)
+    out_bf16 = _check_out_dtype(out_dtype)
+    if a.fwd.data.dtype != torch.float32 or values.dtype != torch.float32:
+        raise ValueError("spmm_bf16 takes a float32 matrix and float32 values")
+    if b.dtype != torch.bfloat16:
+        raise ValueError("b must be torch.bfloat16")
+    if values.dim() != 1 or values.shape[0] != a.fwd.nnz:
+        raise ValueError(f"values must hold the {a.fwd.nnz} entries of A")
+    if b.dim() != 2 or b.shape[0] != a.fwd.num_cols:
+        raise ValueError(f"A has {a.fwd.num_cols} columns: b must be [{a.fwd.num_cols}, N], not {tuple(b.shape)}")
+    if b.shape[1] > 1 and b.stride(1) != 1:
+        raise ValueError("b must have unit column stride")
+    if acc not in ("reference", "fast"):
+        raise ValueError(f"acc must be 'reference' or 'fast', not {acc!r}")
+    return _SpmmCsrBf16.apply(values, b, a, out_bf16, acc)

@@ -1206,3 +1206,72 @@ def shard_rows_by_nnz(row_ptrs, parts):
     bounds = np.zeros(parts + 1, dtype=np.uint32)
     capi.check(capi.lib().mispmm_shard_rows_by_nnz_host(rp.shape[0] - 1, rp.ctypes.data, parts, bounds.ctypes.data))
     return bounds
+
+
+# ---- the row-list product with B in bf16 (libmispmm_bf16.so, include/mispmm_bf16.h)
+def _spmm_rows_bf16(what, num_rows, num_cols, nnz, row_ptrs, row_nnz, col_idxs, data, b_bf16, out_bf16, out, acc, sum_f32, stream):
+    """C = A @ B from A's row list through mispmm_rows_bf16: A's values fp32, B int16 bf16 bits, C float32 or int16 bf16
+    bits.  row_ptrs=None: every row holds row_nnz entries (0xFFFFFFFF = padding).  Exact contracts, see the header."""
+    from . import capi_bf16
+    _require_gpu(col_idxs, data, b_bf16, out)
+    if data.dtype != torch.float32:
+        raise ValueError(f"{what} takes a float32 matrix, not {data.dtype}")
+    if acc not in capi.ACC_MODES:
+        raise ValueError(f"acc must be one of {sorted(capi.ACC_MODES)}, not {acc!r}")
+    ldb = _bf16_ld(b_bf16, "b_bf16")
+    if b_bf16.shape[0] != num_cols:
+        raise ValueError(f"B has {b_bf16.shape[0]} rows, A has {num_cols} columns")
+    n = b_bf16.shape[1]
+    dtype = torch.int16 if out_bf16 else torch.float32
+    if out is None:
+        out = torch.empty((num_rows, n), dtype=dtype, device=b_bf16.device)
+    if out.dim() != 2 or out.dtype != dtype or tuple(out.shape) != (num_rows, n) or out.stride(1) != 1 and n > 1:
+        raise ValueError(f"out must be a 2-D {dtype} tensor of shape {(num_rows, n)} with unit column stride")
+    ldc = out.stride(0) if num_rows > 1 else max(n, out.stride(0))
+    if ldc < n:
+        raise ValueError(f"out must not overlap its own rows (row stride {ldc} < {n} columns)")
+    capi_bf16.check(capi_bf16.lib().mispmm_rows_bf16(_stream_ptr(stream), num_rows, num_cols, nnz, _p(row_ptrs), int(row_nnz), _p(col_idxs),
+                                                     _p(data), _p(b_bf16), n, ldb, _p(out), ldc, int(bool(out_bf16)), capi.ACC_MODES[acc],
+                                                     int(bool(sum_f32))))
+    return out
+
+
+def spmm_csr_bf16(a, b_bf16, out_bf16=False, out=None, acc="reference", ref_sum="f64", stream=None):
+    """C = A @ B with B in bf16 (mispmm_rows_bf16).  a: any float32 DeviceCSR -- a CSR, or the list of bsr_nonzeros (pass
+    ref_sum="f32" for that one: the fp32 sum of the BSR reference); b_bf16: [K, N] int16 tensor of bf16 bits, unit column
+    stride, any row stride; returns [M, N] float32, or int16 bf16 bits with out_bf16.  acc="reference": the fp32 product
+    summed in a double (ref_sum="f64", the CSR rule) or in fp32 (ref_sum="f32"); acc="fast": one fma per entry.  Plan and
+    span list are not used; a matrix of uniform rows is walked without its row pointers (MISPMM_NO_HINT=1: with them)."""
+    if ref_sum not in ("f64", "f32"):
+        raise ValueError(f"ref_sum must be 'f64' or 'f32', not {ref_sum!r}")
+    _require_gpu(a.row_ptrs)
+    uniform = a.uniform_row_nnz and os.environ.get("MISPMM_NO_HINT") != "1"
+    return _spmm_rows_bf16("spmm_csr_bf16", a.num_rows, a.num_cols, a.nnz, None if uniform else a.row_ptrs, a.uniform_row_nnz if uniform else 0,
+                           a.col_idxs, a.data, b_bf16, out_bf16, out, acc, ref_sum == "f32", stream)
+
+
+def spmm_coo_bf16(a, b_bf16, out_bf16=False, out=None, acc="reference", stream=None):
+    """C = A @ B with B in bf16 for a float32 DeviceCOO (entries stable-sorted by row at upload): fp32 product, fp32 sum in
+    list order (the COO reference's rule), or acc="fast".  The row boundaries are built by coo_row_bounds on first use and
+    kept in a.row_bounds.  Operands as spmm_csr_bf16."""
+    _require_gpu(a.row_idxs)
+    if a.data.dtype != torch.float32:
+        raise ValueError(f"spmm_coo_bf16 takes a float32 matrix, not {a.data.dtype}")
+    if a.row_bounds is None:
+        a.row_bounds = coo_row_bounds(a, stream)
+    return _spmm_rows_bf16("spmm_coo_bf16", a.num_rows, a.num_cols, a.nnz, a.row_bounds, 0, a.col_idxs, a.data, b_bf16, out_bf16, out, acc, True,
+                           stream)
+
+
+def spmm_ell_bf16(a, b_bf16, out_bf16=False, out=None, acc="reference", stream=None):
+    """C = A @ B with B in bf16 for a float32 DeviceELL: the list of occupied slots where the upload made one (`compact`),
+    else the padded row-major arrays as a uniform list of `width` entries per row, the padding skipped by its column index.
+    fp32 product, fp32 sum in slot order (the ELL reference's rule), or acc="fast".  Operands as spmm_csr_bf16."""
+    _require_gpu(a.col_idxs)
+    if a.data.dtype != torch.float32:
+        raise ValueError(f"spmm_ell_bf16 takes a float32 matrix, not {a.data.dtype}")
+    if a.compact is not None:
+        nnz, rp, ci, va = a.compact[:4]
+        return _spmm_rows_bf16("spmm_ell_bf16", a.num_rows, a.num_cols, nnz, rp, 0, ci, va, b_bf16, out_bf16, out, acc, True, stream)
+    return _spmm_rows_bf16("spmm_ell_bf16", a.num_rows, a.num_cols, a.num_rows * a.width, None, a.width, a.col_idxs, a.data, b_bf16, out_bf16, out,
+                           acc, True, stream)
