@@ -706,3 +706,89 @@ extern "C" int mispmm_csr_transpose_host(uint32_t M, uint32_t K, uint32_t nnz, c
     }
     return MISPMM_OK;
 }
+
+// ---- structure checks (the validity contract of mispmm.h): one pass over the index arrays, nothing launched.  Each names the
+// first defect it meets -- which array, which position, the value and the bound -- in mispmm_last_error().
+namespace {
+using ull = unsigned long long;
+
+// pointers of `rows` rows: rows + 1 entries, first 0, non-decreasing, last == total
+int check_row_pointers(const char *who, const char *name, const char *rowsName, uint32_t rows, const uint32_t *ptrs, uint64_t numPtrs,
+                       const char *totalName, uint32_t total) {
+    if (numPtrs != static_cast<uint64_t>(rows) + 1u)
+        return fail(MISPMM_ERR_INVALID_ARG, "%s check: %s holds %llu entries, %s + 1 = %llu are needed", who, name, static_cast<ull>(numPtrs),
+                    rowsName, static_cast<ull>(rows) + 1u);
+    if (!ptrs) return fail(MISPMM_ERR_INVALID_ARG, "%s check: %s is null", who, name);
+    if (ptrs[0] != 0) return fail(MISPMM_ERR_INVALID_ARG, "%s check: %s[0] = %u, must be 0", who, name, ptrs[0]);
+    for (uint32_t r = 0; r < rows; ++r)
+        if (ptrs[r + 1] < ptrs[r])
+            return fail(MISPMM_ERR_INVALID_ARG, "%s check: %s decrease at row %u (%u then %u)", who, name, r, ptrs[r], ptrs[r + 1]);
+    if (ptrs[rows] != total)
+        return fail(MISPMM_ERR_INVALID_ARG, "%s check: %s[%s = %u] = %u, %s = %u", who, name, rowsName, rows, ptrs[rows], totalName, total);
+    return MISPMM_OK;
+}
+
+int check_length(const char *who, const char *name, uint64_t have, const char *needName, uint64_t need) {
+    if (have != need)
+        return fail(MISPMM_ERR_INVALID_ARG, "%s check: %s holds %llu entries, %s = %llu are needed", who, name, static_cast<ull>(have), needName,
+                    static_cast<ull>(need));
+    return MISPMM_OK;
+}
+
+int check_below(const char *who, const char *name, const uint32_t *idxs, uint64_t count, const char *boundName, uint32_t bound) {
+    if (count != 0 && !idxs) return fail(MISPMM_ERR_INVALID_ARG, "%s check: %s is null", who, name);
+    for (uint64_t i = 0; i < count; ++i)
+        if (idxs[i] >= bound)
+            return fail(MISPMM_ERR_INVALID_ARG, "%s check: %s[%llu] = %u is not below %s = %u", who, name, static_cast<ull>(i), idxs[i], boundName,
+                        bound);
+    return MISPMM_OK;
+}
+}  // namespace
+
+extern "C" int mispmm_csr_check_host(uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs_host, uint64_t numRowPtrs,
+                                     const uint32_t *colIdxs_host, uint64_t numColIdxs) {
+    if (int st = check_row_pointers("csr", "rowPtrs", "M", M, rowPtrs_host, numRowPtrs, "nnz", nnz)) return st;
+    if (int st = check_length("csr", "colIdxs", numColIdxs, "nnz", nnz)) return st;
+    return check_below("csr", "colIdxs", colIdxs_host, nnz, "K", K);
+}
+
+extern "C" int mispmm_coo_check_host(uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowIdxs_host, uint64_t numRowIdxs,
+                                     const uint32_t *colIdxs_host, uint64_t numColIdxs) {
+    if (int st = check_length("coo", "rowIdxs", numRowIdxs, "nnz", nnz)) return st;
+    if (int st = check_length("coo", "colIdxs", numColIdxs, "nnz", nnz)) return st;
+    if (int st = check_below("coo", "rowIdxs", rowIdxs_host, nnz, "M", M)) return st;
+    return check_below("coo", "colIdxs", colIdxs_host, nnz, "K", K);
+}
+
+extern "C" int mispmm_ell_check_host(int layout, uint32_t M, uint32_t K, uint32_t width, const uint32_t *idxs_host, uint64_t numIdxs) {
+    if (layout != MISPMM_ELL_COLUMN_MAJOR && layout != MISPMM_ELL_ROW_MAJOR)
+        return fail(MISPMM_ERR_INVALID_ARG, "ell check: layout %d is neither column-major (0) nor row-major (1)", layout);
+    const bool colMajor = layout == MISPMM_ELL_COLUMN_MAJOR;
+    const char *name = colMajor ? "rowIdxs" : "colIdxs";
+    const uint64_t slots = static_cast<uint64_t>(colMajor ? K : M) * width;
+    if (int st = check_length("ell", name, numIdxs, colMajor ? "K * maxColNnz" : "M * width", slots)) return st;
+    if (slots != 0 && !idxs_host) return fail(MISPMM_ERR_INVALID_ARG, "ell check: %s is null", name);
+    const uint32_t bound = colMajor ? M : K;
+    for (uint64_t i = 0; i < slots; ++i) {
+        const uint32_t v = idxs_host[i];
+        // column-major: any index with the sign bit set is padding; row-major: 0xFFFFFFFF alone, the value the kernels drop
+        if (colMajor ? static_cast<int32_t>(v) < 0 : v == 0xFFFFFFFFu) continue;
+        if (v >= bound)
+            return fail(MISPMM_ERR_INVALID_ARG, "ell check: %s[%llu] = %u is not below %s = %u%s", name, static_cast<ull>(i), v,
+                        colMajor ? "M" : "K", bound, colMajor ? "" : " (padding is 4294967295 alone)");
+    }
+    return MISPMM_OK;
+}
+
+extern "C" int mispmm_bsr_check_host(uint32_t M, uint32_t K, uint32_t bR, uint32_t bC, uint32_t numBlocks, const uint32_t *blockRowPtrs_host,
+                                     uint64_t numBlockRowPtrs, const uint32_t *blockColIdxs_host, uint64_t numBlockColIdxs,
+                                     uint64_t numValues) {
+    if (bR == 0 || bC == 0) return fail(MISPMM_ERR_INVALID_ARG, "bsr check: block shape %u x %u must be positive", bR, bC);
+    if (M % bR != 0) return fail(MISPMM_ERR_INVALID_ARG, "bsr check: M = %u is not a multiple of bR = %u", M, bR);
+    if (K % bC != 0) return fail(MISPMM_ERR_INVALID_ARG, "bsr check: K = %u is not a multiple of bC = %u", K, bC);
+    if (int st = check_row_pointers("bsr", "blockRowPtrs", "M / bR", M / bR, blockRowPtrs_host, numBlockRowPtrs, "numBlocks", numBlocks))
+        return st;
+    if (int st = check_length("bsr", "blockColIdxs", numBlockColIdxs, "numBlocks", numBlocks)) return st;
+    if (int st = check_below("bsr", "blockColIdxs", blockColIdxs_host, numBlocks, "K / bC", K / bC)) return st;
+    return check_length("bsr", "data", numValues, "numBlocks * bR * bC", static_cast<uint64_t>(numBlocks) * bR * bC);
+}

@@ -6,6 +6,7 @@
 #include <map>
 
 #include "formats/dense.hpp"
+#include "formats/ingest.hpp"
 
 namespace cuspmm {
 
@@ -58,6 +59,10 @@ template <typename _dataT, typename _metaT> class SparseMatrixCSR : public Spars
     ~SparseMatrixCSR() override;
 
     const char *formatName() const override { return "CSR"; }
+    // The validity contract of mispmm.h on the host arrays (mispmm_csr_check_host): throws std::runtime_error
+    // "<origin>: <first defect>".  Every file constructor ends with it and every copy2Device() begins with it.
+    void validate(const std::string &origin) const;
+    void release();  // frees every buffer (what the destructor does)
     SparseMatrixCSR<DT, MT> *copy2Device();
     bool allocateSpace(bool onDevice);
     DenseMatrix<DT, MT> *toDense();
@@ -88,6 +93,8 @@ template <typename _dataT, typename _metaT> class SparseMatrixCOO : public Spars
     ~SparseMatrixCOO() override;
 
     const char *formatName() const override { return "COO"; }
+    void validate(const std::string &origin) const;  // mispmm_coo_check_host, as SparseMatrixCSR::validate
+    void release();
     SparseMatrixCOO<DT, MT> *copy2Device();
     bool allocateSpace(bool onDevice);
     DenseMatrix<DT, MT> *toDense();
@@ -126,6 +133,8 @@ template <typename _dataT, typename _metaT> class SparseMatrixELL : public Spars
     ~SparseMatrixELL() override;
 
     const char *formatName() const override { return "ELL"; }
+    void validate(const std::string &origin) const;  // mispmm_ell_check_host (column-major), as SparseMatrixCSR::validate
+    void release();
     bool allocateSpace(bool onDevice);
     SparseMatrixELL<DT, MT> *copy2Device();
     DenseMatrix<DT, MT> *toDense();
@@ -165,6 +174,8 @@ template <typename _dataT, typename _metaT> class SparseMatrixBSR : public Spars
     ~SparseMatrixBSR() override;
 
     const char *formatName() const override { return "BSR"; }
+    void validate(const std::string &origin) const;  // mispmm_bsr_check_host, as SparseMatrixCSR::validate
+    void release();
     bool copyData(SparseMatrixBSR<DT, MT> *source, bool onDevice);
     SparseMatrixBSR<DT, MT> *copy2Device();
     void assertCheck();

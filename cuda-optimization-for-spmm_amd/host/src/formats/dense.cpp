@@ -1,4 +1,5 @@
 #include "formats/dense.hpp"
+#include "formats/ingest.hpp"
 
 #include <iomanip>
 #include <limits>
@@ -6,25 +7,30 @@
 
 namespace cuspmm {
 
-static std::ifstream openOrThrow(const std::string &path) {
-    std::ifstream f(path);
-    if (!f.is_open()) {
-        std::cerr << "File " << path << " doesn't exist!" << std::endl;
-        throw std::runtime_error("cannot open " + path);
-    }
-    return f;
-}
-
 template <typename DT, typename MT> DenseMatrix<DT, MT>::DenseMatrix(std::string filePath) {
-    std::ifstream in = openOrThrow(filePath);
+    TextFile in(filePath, "dense");
     std::string line;
-    in >> this->numRows >> this->numCols;
-    std::getline(in, line);  // rest of the header (the converter appends a non-zero count)
+    // the header line: two counts; whatever follows them on the line is ignored (the converter appends a non-zero count)
+    if (!in.line(line)) in.bad("header is not two numbers: the file is empty");
+    {
+        std::istringstream head(line);
+        long long rows = -1, cols = -1;
+        head >> rows >> cols;
+        if (head.fail() || rows < 0 || cols < 0 || rows > 0xFFFFFFFFll || cols > 0xFFFFFFFFll)
+            in.bad("header is not two numbers: '" + line + "'");
+        this->numRows = (MT)rows;
+        this->numCols = (MT)cols;
+    }
+    in.promise(2 + (uint64_t)this->numRows * this->numCols);
     this->allocateSpace(false);
-    for (MT r = 0; r < this->numRows; ++r) {
-        if (!std::getline(in, line)) throw std::runtime_error(filePath + ": fewer rows than the header says");
-        std::istringstream row(line);
-        for (MT c = 0; c < this->numCols; ++c) row >> this->data[RowMjIdx(r, c, this->numCols)];
+    try {
+        for (MT r = 0; r < this->numRows; ++r) {
+            if (!in.line(line)) in.bad("fewer rows than the header says: row " + std::to_string(r) + " is missing");
+            in.numbersOfLine(line, r, this->numCols, this->data + RowMjIdx(r, 0, this->numCols));
+        }
+    } catch (...) {
+        this->freeSpace();  // a constructor that throws runs no destructor
+        throw;
     }
 }
 

@@ -5,23 +5,41 @@
 namespace cuspmm {
 
 template <typename DT, typename MT> SparseMatrixBSR<DT, MT>::SparseMatrixBSR(std::string filePath) {
-    std::ifstream in(filePath);
-    if (!in.is_open()) {
-        std::cerr << "File " << filePath << " doesn't exist!" << std::endl;
-        throw std::runtime_error("cannot open " + filePath);
-    }
-    in >> this->numRows >> this->numCols >> this->numNonZero >> this->blockRowSize >> this->blockColSize >>
-        this->numBlocks;
-    if (in.fail() || this->blockRowSize == 0 || this->blockColSize == 0)
-        throw std::runtime_error(filePath + ": malformed .bsr header");
+    TextFile in(filePath, ".bsr");
+    this->numRows = in.count("numRows");
+    this->numCols = in.count("numCols");
+    this->numNonZero = in.count("numNonZero");
+    this->blockRowSize = in.count("blockRowSize");
+    this->blockColSize = in.count("blockColSize");
+    this->numBlocks = in.count("numBlocks");
+    // the shape conditions of the structure check, ahead of it: the array sizes below divide by the block shape
+    if (this->blockRowSize == 0 || this->blockColSize == 0)
+        in.bad("bsr check: block shape " + std::to_string(this->blockRowSize) + " x " + std::to_string(this->blockColSize) + " must be positive");
+    if (this->numRows % this->blockRowSize != 0)
+        in.bad("bsr check: M = " + std::to_string(this->numRows) + " is not a multiple of bR = " + std::to_string(this->blockRowSize));
     this->numBlockRows = this->numRows / this->blockRowSize;
-    this->numElements = this->numBlocks * this->blockRowSize * this->blockColSize;
+    const uint64_t elements = (uint64_t)this->numBlocks * this->blockRowSize * this->blockColSize;
+    in.promise(6 + ((uint64_t)this->numBlockRows + 1) + this->numBlocks + elements);
+    if (elements > 0xFFFFFFFFull) in.bad("more than 2^32 - 1 block values");
+    this->numElements = (MT)elements;
     this->allocateSpace(false);
-    for (size_t i = 0; i <= this->numBlockRows; ++i) in >> this->blockRowPtrs[i];
-    for (size_t i = 0; i < this->numBlocks; ++i) in >> this->blockColIdxs[i];
-    for (size_t i = 0; i < this->numElements; ++i) in >> this->data[i];
-    if (in.fail()) throw std::runtime_error(filePath + ": truncated or malformed .bsr file");
-    this->assertCheck();
+    try {
+        for (size_t i = 0; i <= this->numBlockRows; ++i) this->blockRowPtrs[i] = in.index("blockRowPtrs", i);
+        for (size_t i = 0; i < this->numBlocks; ++i) this->blockColIdxs[i] = in.index("blockColIdxs", i);
+        for (size_t i = 0; i < this->numElements; ++i) this->data[i] = in.template value<DT>("data", i);
+        this->validate(filePath + ": malformed .bsr file");
+    } catch (...) {
+        this->release();  // a constructor that throws runs no destructor
+        throw;
+    }
+}
+
+template <typename DT, typename MT> void SparseMatrixBSR<DT, MT>::validate(const std::string &origin) const {
+    if (this->onDevice) throw std::runtime_error(origin + ": the structure check reads host arrays");
+    throwIfInvalid(mispmm_bsr_check_host(this->numRows, this->numCols, this->blockRowSize, this->blockColSize, this->numBlocks,
+                                         this->blockRowPtrs, (uint64_t)this->numBlockRows + 1, this->blockColIdxs, this->numBlocks,
+                                         this->numElements),
+                   origin);
 }
 
 template <typename DT, typename MT>
@@ -46,7 +64,9 @@ SparseMatrixBSR<DT, MT>::SparseMatrixBSR(SparseMatrixBSR<DT, MT> *target, bool o
     this->copyData(target, onDevice);
 }
 
-template <typename DT, typename MT> SparseMatrixBSR<DT, MT>::~SparseMatrixBSR() {
+template <typename DT, typename MT> SparseMatrixBSR<DT, MT>::~SparseMatrixBSR() { this->release(); }
+
+template <typename DT, typename MT> void SparseMatrixBSR<DT, MT>::release() {
     releaseBuffer(this->blockRowPtrs, this->onDevice);
     releaseBuffer(this->blockColIdxs, this->onDevice);
     releaseBuffer(this->data, this->onDevice);
@@ -54,6 +74,8 @@ template <typename DT, typename MT> SparseMatrixBSR<DT, MT>::~SparseMatrixBSR() 
     releaseBuffer(this->nzSpans, true);
     releaseBuffer(this->nzColIdxs, true);
     releaseBuffer(this->nzVals, true);
+    this->blockRowPtrs = this->blockColIdxs = this->nzRowPtrs = this->nzSpans = this->nzColIdxs = nullptr;
+    this->data = this->nzVals = nullptr;
 }
 
 template <typename DT, typename MT> bool SparseMatrixBSR<DT, MT>::allocateSpace(bool onDevice) {
@@ -78,6 +100,9 @@ template <typename DT, typename MT> bool SparseMatrixBSR<DT, MT>::copyData(Spars
 }
 
 template <typename DT, typename MT> SparseMatrixBSR<DT, MT> *SparseMatrixBSR<DT, MT>::copy2Device() {
+    // before any device allocation: covers matrices filled in memory through the class API, and stands in for the non-zero
+    // builders below, which cannot check block columns themselves (their signatures carry no K)
+    this->validate("BSR copy2Device");
     assert(!this->onDevice && this->data != nullptr);
     auto *d = new SparseMatrixBSR<DT, MT>(this, true);
     if constexpr (std::is_same_v<DT, float>) {

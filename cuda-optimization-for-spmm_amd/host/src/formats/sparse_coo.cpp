@@ -5,15 +5,30 @@
 namespace cuspmm {
 
 template <typename DT, typename MT> SparseMatrixCOO<DT, MT>::SparseMatrixCOO(std::string filePath) {
-    std::ifstream in(filePath);
-    if (!in.is_open()) {
-        std::cerr << "File " << filePath << " doesn't exist!" << std::endl;
-        throw std::runtime_error("cannot open " + filePath);
-    }
-    in >> this->numRows >> this->numCols >> this->numNonZero;
+    TextFile in(filePath, ".coo");
+    this->numRows = in.count("numRows");
+    this->numCols = in.count("numCols");
+    this->numNonZero = in.count("numNonZero");
+    in.promise(3 + 3 * (uint64_t)this->numNonZero);
     this->allocateSpace(false);
-    for (size_t i = 0; i < this->numNonZero; ++i) in >> this->rowIdxs[i] >> this->colIdxs[i] >> this->data[i];
-    if (in.fail()) throw std::runtime_error(filePath + ": truncated or malformed .coo file");
+    try {
+        for (size_t i = 0; i < this->numNonZero; ++i) {
+            this->rowIdxs[i] = in.index("rowIdxs", i);
+            this->colIdxs[i] = in.index("colIdxs", i);
+            this->data[i] = in.template value<DT>("data", i);
+        }
+        this->validate(filePath + ": malformed .coo file");
+    } catch (...) {
+        this->release();  // a constructor that throws runs no destructor
+        throw;
+    }
+}
+
+template <typename DT, typename MT> void SparseMatrixCOO<DT, MT>::validate(const std::string &origin) const {
+    if (this->onDevice) throw std::runtime_error(origin + ": the structure check reads host arrays");
+    throwIfInvalid(mispmm_coo_check_host(this->numRows, this->numCols, this->numNonZero, this->rowIdxs, this->numNonZero, this->colIdxs,
+                                         this->numNonZero),
+                   origin);
 }
 
 template <typename DT, typename MT>
@@ -24,12 +39,16 @@ SparseMatrixCOO<DT, MT>::SparseMatrixCOO(MT numRows, MT numCols, MT numNonZero, 
     this->allocateSpace(onDevice);
 }
 
-template <typename DT, typename MT> SparseMatrixCOO<DT, MT>::~SparseMatrixCOO() {
+template <typename DT, typename MT> SparseMatrixCOO<DT, MT>::~SparseMatrixCOO() { this->release(); }
+
+template <typename DT, typename MT> void SparseMatrixCOO<DT, MT>::release() {
     releaseBuffer(this->rowIdxs, this->onDevice);
     releaseBuffer(this->colIdxs, this->onDevice);
     releaseBuffer(this->data, this->onDevice);
     releaseBuffer(this->rowBoundsWorkspace, true);
     releaseBuffer(this->rowSpans, true);
+    this->rowIdxs = this->colIdxs = this->rowBoundsWorkspace = this->rowSpans = nullptr;
+    this->data = nullptr;
 }
 
 template <typename DT, typename MT> bool SparseMatrixCOO<DT, MT>::allocateSpace(bool onDevice) {
@@ -43,6 +62,7 @@ template <typename DT, typename MT> bool SparseMatrixCOO<DT, MT>::allocateSpace(
 }
 
 template <typename DT, typename MT> SparseMatrixCOO<DT, MT> *SparseMatrixCOO<DT, MT>::copy2Device() {
+    this->validate("COO copy2Device");  // before any device allocation: covers matrices filled in memory through the class API
     assert(!this->onDevice && this->data != nullptr);
     auto *d = new SparseMatrixCOO<DT, MT>(this->numRows, this->numCols, this->numNonZero, true);
     const MT *rows = this->rowIdxs, *cols = this->colIdxs;

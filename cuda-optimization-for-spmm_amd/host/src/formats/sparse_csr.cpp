@@ -6,18 +6,29 @@
 namespace cuspmm {
 
 template <typename DT, typename MT> SparseMatrixCSR<DT, MT>::SparseMatrixCSR(std::string filePath) {
-    std::ifstream in(filePath);
-    if (!in.is_open()) {
-        std::cerr << "File " << filePath << " doesn't exist!" << std::endl;
-        throw std::runtime_error("cannot open " + filePath);
-    }
-    in >> this->numRows >> this->numCols >> this->numNonZero;
+    TextFile in(filePath, ".csr");
+    this->numRows = in.count("numRows");
+    this->numCols = in.count("numCols");
+    this->numNonZero = in.count("numNonZero");
+    in.promise(3 + ((uint64_t)this->numRows + 1) + 2 * (uint64_t)this->numNonZero);
     this->allocateSpace(false);
-    // three whitespace-separated arrays; the text format puts one per line but only the counts matter
-    for (size_t i = 0; i <= this->numRows; ++i) in >> this->rowPtrs[i];
-    for (size_t i = 0; i < this->numNonZero; ++i) in >> this->colIdxs[i];
-    for (size_t i = 0; i < this->numNonZero; ++i) in >> this->data[i];
-    if (in.fail()) throw std::runtime_error(filePath + ": truncated or malformed .csr file");
+    try {
+        // three whitespace-separated arrays; the text format puts one per line but only the counts matter
+        for (size_t i = 0; i <= this->numRows; ++i) this->rowPtrs[i] = in.index("rowPtrs", i);
+        for (size_t i = 0; i < this->numNonZero; ++i) this->colIdxs[i] = in.index("colIdxs", i);
+        for (size_t i = 0; i < this->numNonZero; ++i) this->data[i] = in.template value<DT>("data", i);
+        this->validate(filePath + ": malformed .csr file");
+    } catch (...) {
+        this->release();  // a constructor that throws runs no destructor
+        throw;
+    }
+}
+
+template <typename DT, typename MT> void SparseMatrixCSR<DT, MT>::validate(const std::string &origin) const {
+    if (this->onDevice) throw std::runtime_error(origin + ": the structure check reads host arrays");
+    throwIfInvalid(mispmm_csr_check_host(this->numRows, this->numCols, this->numNonZero, this->rowPtrs, (uint64_t)this->numRows + 1,
+                                         this->colIdxs, this->numNonZero),
+                   origin);
 }
 
 template <typename DT, typename MT>
@@ -28,7 +39,9 @@ SparseMatrixCSR<DT, MT>::SparseMatrixCSR(MT numRows, MT numCols, MT numNonZero, 
     this->allocateSpace(onDevice);
 }
 
-template <typename DT, typename MT> SparseMatrixCSR<DT, MT>::~SparseMatrixCSR() {
+template <typename DT, typename MT> SparseMatrixCSR<DT, MT>::~SparseMatrixCSR() { this->release(); }
+
+template <typename DT, typename MT> void SparseMatrixCSR<DT, MT>::release() {
     releaseBuffer(this->rowPtrs, this->onDevice);
     releaseBuffer(this->colIdxs, this->onDevice);
     releaseBuffer(this->data, this->onDevice);
@@ -37,6 +50,8 @@ template <typename DT, typename MT> SparseMatrixCSR<DT, MT>::~SparseMatrixCSR() 
     releaseBuffer(this->planColIdxs, this->onDevice);
     releaseBuffer(this->planData, this->onDevice);
     releaseBuffer(this->planRowMap, this->onDevice);
+    this->rowPtrs = this->colIdxs = this->rowSpans = this->planRowPtrs = this->planColIdxs = this->planRowMap = nullptr;
+    this->data = this->planData = nullptr;
 }
 
 template <typename DT, typename MT> bool SparseMatrixCSR<DT, MT>::allocateSpace(bool onDevice) {
@@ -72,6 +87,7 @@ uint32_t *uploadRowSpans(uint32_t numRows, const uint32_t *rowPtrsHost, uint32_t
 }
 
 template <typename DT, typename MT> SparseMatrixCSR<DT, MT> *SparseMatrixCSR<DT, MT>::copy2Device() {
+    this->validate("CSR copy2Device");  // before any device allocation: covers matrices filled in memory through the class API
     assert(!this->onDevice && this->rowPtrs != nullptr);
     auto *d = new SparseMatrixCSR<DT, MT>(this->numRows, this->numCols, this->numNonZero, true);
     copyBuffer(d->rowPtrs, true, this->rowPtrs, false, ((size_t)this->numRows + 1) * sizeof(MT));

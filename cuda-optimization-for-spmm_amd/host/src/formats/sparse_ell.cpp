@@ -6,25 +6,31 @@ namespace cuspmm {
 
 template <typename DT, typename MT>
 SparseMatrixELL<DT, MT>::SparseMatrixELL(std::string rowindPath, std::string valuesPath) {
-    std::ifstream idx(rowindPath), val(valuesPath);
-    if (!idx.is_open()) {
-        std::cerr << "File " << rowindPath << " doesn't exist!" << std::endl;
-        throw std::runtime_error("cannot open " + rowindPath);
-    }
-    if (!val.is_open()) {
-        std::cerr << "File " << valuesPath << " doesn't exist!" << std::endl;
-        throw std::runtime_error("cannot open " + valuesPath);
-    }
-    idx >> this->numRows >> this->numCols >> this->numNonZero >> this->maxColNnz;
-    this->allocateSpace(false);
+    TextFile idx(rowindPath, "ELL"), val(valuesPath, "ELL");
+    this->numRows = idx.count("numRows");
+    this->numCols = idx.count("numCols");
+    this->numNonZero = idx.count("numNonZero");
+    this->maxColNnz = idx.count("maxColNnz");
     const size_t slots = this->numSlots();
-    for (size_t i = 0; i < slots; ++i) {
-        long long v;  // "-1" marks padding; stored as 0xFFFFFFFF like `istream >> uint32_t` does
-        idx >> v;
-        this->rowIdxs[i] = (MT)v;
+    idx.promise(4 + (uint64_t)slots);
+    val.promise(slots);
+    this->allocateSpace(false);
+    try {
+        // "-1" marks padding; stored as 0xFFFFFFFF like `istream >> uint32_t` does.  Any index with the sign bit set is padding
+        // (the reference's `if (row >= 0)`), so the tokens may go down to -2^31; the structure check decides about the others.
+        for (size_t i = 0; i < slots; ++i) this->rowIdxs[i] = idx.index("rowIdxs", i, -0x80000000ll);
+        for (size_t i = 0; i < slots; ++i) this->data[i] = val.template value<DT>("data", i);
+        this->validate(rowindPath + ": malformed ELL file");
+    } catch (...) {
+        this->release();  // a constructor that throws runs no destructor
+        throw;
     }
-    for (size_t i = 0; i < slots; ++i) val >> this->data[i];
-    if (idx.fail() || val.fail()) throw std::runtime_error(rowindPath + ": truncated or malformed ELL files");
+}
+
+template <typename DT, typename MT> void SparseMatrixELL<DT, MT>::validate(const std::string &origin) const {
+    if (this->onDevice) throw std::runtime_error(origin + ": the structure check reads host arrays");
+    throwIfInvalid(mispmm_ell_check_host(MISPMM_ELL_COLUMN_MAJOR, this->numRows, this->numCols, this->maxColNnz, this->rowIdxs, this->numSlots()),
+                   origin);
 }
 
 template <typename DT, typename MT>
@@ -36,7 +42,9 @@ SparseMatrixELL<DT, MT>::SparseMatrixELL(MT numRows, MT numCols, MT numNonZero, 
     this->allocateSpace(onDevice);
 }
 
-template <typename DT, typename MT> SparseMatrixELL<DT, MT>::~SparseMatrixELL() {
+template <typename DT, typename MT> SparseMatrixELL<DT, MT>::~SparseMatrixELL() { this->release(); }
+
+template <typename DT, typename MT> void SparseMatrixELL<DT, MT>::release() {
     releaseBuffer(this->rowIdxs, this->onDevice);
     releaseBuffer(this->data, this->onDevice);
     releaseBuffer(this->rmColIdxs, true);
@@ -45,6 +53,8 @@ template <typename DT, typename MT> SparseMatrixELL<DT, MT>::~SparseMatrixELL() 
     releaseBuffer(this->cpColIdxs, true);
     releaseBuffer(this->cpData, true);
     releaseBuffer(this->cpSpans, true);
+    this->rowIdxs = this->rmColIdxs = this->cpRowPtrs = this->cpColIdxs = this->cpSpans = nullptr;
+    this->data = this->rmData = this->cpData = nullptr;
 }
 
 template <typename DT, typename MT> bool SparseMatrixELL<DT, MT>::allocateSpace(bool onDevice) {
@@ -56,6 +66,7 @@ template <typename DT, typename MT> bool SparseMatrixELL<DT, MT>::allocateSpace(
 }
 
 template <typename DT, typename MT> SparseMatrixELL<DT, MT> *SparseMatrixELL<DT, MT>::copy2Device() {
+    this->validate("ELL copy2Device");  // before any device allocation: covers matrices filled in memory through the class API
     assert(!this->onDevice && this->data != nullptr);
     auto *d = new SparseMatrixELL<DT, MT>(this->numRows, this->numCols, this->numNonZero, this->maxColNnz, true);
     copyBuffer(d->rowIdxs, true, this->rowIdxs, false, this->numSlots() * sizeof(MT));

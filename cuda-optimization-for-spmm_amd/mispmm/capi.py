@@ -118,7 +118,12 @@ SIGNATURES = {
     "mispmm_multi_bsrc_slots_bf16": (_i, [_u32, _c.POINTER(_i), _pvp, _c.POINTER(_u32), _u32, _c.POINTER(_u32), _pvp, _pvp, _pvp, _pvp,
                                           _u32, _u32, _pvp, _u32, _i, _i, _vp]),
     "mispmm_slab_scatter": (_i, [_vp, _vp, _sz, _pvp, _u32]),
+    "mispmm_csr_check_host": (_i, [_u32, _u32, _u32, _vp, _c.c_uint64, _vp, _c.c_uint64]),
+    "mispmm_coo_check_host": (_i, [_u32, _u32, _u32, _vp, _c.c_uint64, _vp, _c.c_uint64]),
+    "mispmm_ell_check_host": (_i, [_i, _u32, _u32, _u32, _vp, _c.c_uint64]),
+    "mispmm_bsr_check_host": (_i, [_u32, _u32, _u32, _u32, _u32, _vp, _c.c_uint64, _vp, _c.c_uint64, _c.c_uint64]),
 }
+ELL_COLUMN_MAJOR, ELL_ROW_MAJOR = 0, 1
 
 _lib = None
 

@@ -267,79 +267,250 @@ def csr_to_bsr(csr, block_row_size, block_col_size=None):
 
 
 # --------------------------------------------------------------------------
+# validity (the contract of include/mispmm.h, restated in numpy; the messages
+# are those of the library's mispmm_*_check_host)
+# --------------------------------------------------------------------------
+def as_u32(name, a):
+    """`a` as a flat uint32 array; a value that is no uint32 is an error, never wrapped."""
+    a = np.asarray(a)
+    if a.dtype != np.uint32:
+        wide = a.astype(np.int64).reshape(-1) if a.dtype.kind in "iub" else None
+        if wide is None:
+            raise ValueError(f"{name} must be an integer array, not {a.dtype}")
+        bad = np.flatnonzero((wide < 0) | (wide > 0xFFFFFFFF))
+        if bad.size:
+            raise ValueError(f"{name}[{int(bad[0])}] = {int(wide[bad[0]])} is not an index (0 .. 4294967295)")
+        a = wide.astype(np.uint32)
+    return np.ascontiguousarray(a).reshape(-1)
+
+
+def _count(who, name, value):
+    if not 0 <= int(value) <= 0xFFFFFFFF:
+        raise ValueError(f"{who} check: {name} = {int(value)} is not a count (0 .. 4294967295)")
+    return int(value)
+
+
+def _check_length(who, name, have, need_name, need):
+    if have != need:
+        raise ValueError(f"{who} check: {name} holds {have} entries, {need_name} = {need} are needed")
+
+
+def _check_row_pointers(who, name, rows_name, rows, ptrs, total_name, total):
+    if ptrs.shape[0] != rows + 1:
+        raise ValueError(f"{who} check: {name} holds {ptrs.shape[0]} entries, {rows_name} + 1 = {rows + 1} are needed")
+    if ptrs[0] != 0:
+        raise ValueError(f"{who} check: {name}[0] = {int(ptrs[0])}, must be 0")
+    down = np.flatnonzero(ptrs[1:] < ptrs[:-1])
+    if down.size:
+        r = int(down[0])
+        raise ValueError(f"{who} check: {name} decrease at row {r} ({int(ptrs[r])} then {int(ptrs[r + 1])})")
+    if ptrs[rows] != total:
+        raise ValueError(f"{who} check: {name}[{rows_name} = {rows}] = {int(ptrs[rows])}, {total_name} = {total}")
+
+
+def _check_below(who, name, idxs, bound_name, bound, live=None, note=""):
+    bad = idxs >= bound if live is None else live & (idxs >= bound)
+    at = np.flatnonzero(bad)
+    if at.size:
+        raise ValueError(f"{who} check: {name}[{int(at[0])}] = {int(idxs[at[0]])} is not below {bound_name} = {bound}{note}")
+
+
+def check_csr(csr):
+    m, k, nnz = _count("csr", "M", csr.num_rows), _count("csr", "K", csr.num_cols), _count("csr", "nnz", csr.nnz)
+    ptrs, cols = as_u32("rowPtrs", csr.row_ptrs), as_u32("colIdxs", csr.col_idxs)
+    _check_row_pointers("csr", "rowPtrs", "M", m, ptrs, "nnz", nnz)
+    _check_length("csr", "colIdxs", cols.shape[0], "nnz", nnz)
+    _check_length("csr", "data", np.asarray(csr.data).size, "nnz", nnz)
+    _check_below("csr", "colIdxs", cols, "K", k)
+
+
+def check_coo(coo):
+    m, k, nnz = _count("coo", "M", coo.num_rows), _count("coo", "K", coo.num_cols), _count("coo", "nnz", coo.nnz)
+    rows, cols = as_u32("rowIdxs", coo.row_idxs), as_u32("colIdxs", coo.col_idxs)
+    _check_length("coo", "rowIdxs", rows.shape[0], "nnz", nnz)
+    _check_length("coo", "colIdxs", cols.shape[0], "nnz", nnz)
+    _check_below("coo", "rowIdxs", rows, "M", m)
+    _check_below("coo", "colIdxs", cols, "K", k)
+
+
+def check_ell(ell):
+    """ELLColMajor: a row index with the sign bit set is padding; ELLRowMajor: 0xFFFFFFFF alone is."""
+    m, k = _count("ell", "M", ell.num_rows), _count("ell", "K", ell.num_cols)
+    if isinstance(ell, ELLColMajor):
+        w, idxs = _count("ell", "maxColNnz", ell.max_col_nnz), as_u32("rowIdxs", ell.row_idxs)
+        _check_length("ell", "rowIdxs", idxs.shape[0], "K * maxColNnz", k * w)
+        _check_length("ell", "data", np.asarray(ell.data).size, "K * maxColNnz", k * w)
+        _check_below("ell", "rowIdxs", idxs, "M", m, live=idxs < 0x80000000)
+    else:
+        w, idxs = _count("ell", "width", ell.width), as_u32("colIdxs", ell.col_idxs)
+        _check_length("ell", "colIdxs", idxs.shape[0], "M * width", m * w)
+        _check_length("ell", "data", np.asarray(ell.data).size, "M * width", m * w)
+        _check_below("ell", "colIdxs", idxs, "K", k, live=idxs != ELL_PAD, note=" (padding is 4294967295 alone)")
+
+
+def check_bsr(bsr):
+    m, k = _count("bsr", "M", bsr.num_rows), _count("bsr", "K", bsr.num_cols)
+    br, bc = _count("bsr", "bR", bsr.block_row_size), _count("bsr", "bC", bsr.block_col_size)
+    nb = _count("bsr", "numBlocks", bsr.num_blocks)
+    if br == 0 or bc == 0:
+        raise ValueError(f"bsr check: block shape {br} x {bc} must be positive")
+    if m % br:
+        raise ValueError(f"bsr check: M = {m} is not a multiple of bR = {br}")
+    if k % bc:
+        raise ValueError(f"bsr check: K = {k} is not a multiple of bC = {bc}")
+    ptrs, cols = as_u32("blockRowPtrs", bsr.block_row_ptrs), as_u32("blockColIdxs", bsr.block_col_idxs)
+    _check_row_pointers("bsr", "blockRowPtrs", "M / bR", m // br, ptrs, "numBlocks", nb)
+    _check_length("bsr", "blockColIdxs", cols.shape[0], "numBlocks", nb)
+    _check_below("bsr", "blockColIdxs", cols, "K / bC", k // bc)
+    _check_length("bsr", "data", np.asarray(bsr.data).size, "numBlocks * bR * bC", nb * br * bc)
+
+
+# --------------------------------------------------------------------------
 # text readers (the formats the reference's C++ constructors parse)
 # --------------------------------------------------------------------------
-def _tokens(line, count, dtype):
-    arr = np.array(line.split()[:count], dtype=np.float64 if dtype is float else np.int64)
-    if arr.shape[0] != count:
-        raise ValueError(f"expected {count} values, found {arr.shape[0]}")
-    return arr
+class _Text:
+    """The whitespace-separated tokens of one text file, read in order.  Every refusal is a ValueError
+    `<path>: malformed <kind> file: <what>`; an index token is range-checked as a signed 64-bit number
+    before it becomes a uint32, so "-1" never wraps silently."""
+
+    def __init__(self, path, kind):
+        self.path, self.kind = path, kind
+        with open(path, "r") as f:
+            self.text = f.read()
+        self.tokens = self.text.split()
+        self.at = 0
+
+    def bad(self, what):
+        raise ValueError(f"{self.path}: malformed {self.kind} file: {what}")
+
+    def promise(self, tokens):
+        """A token needs at least two bytes (itself and a separator): refuse a header that promises more than the
+        file can hold before anything is allocated."""
+        if tokens * 2 > len(self.text) + 1:
+            self.bad(f"header promises {tokens} tokens, the file has {len(self.text)} bytes")
+
+    def take(self, name, count):
+        got = self.tokens[self.at:self.at + count]
+        if len(got) != count:
+            self.bad(f"truncated: {name} holds {len(got)} tokens, {count} are needed")
+        self.at += count
+        return got
+
+    def numbers(self, toks, dtype, label):
+        try:
+            return np.array(toks, dtype=dtype)
+        except (ValueError, OverflowError):
+            for i, t in enumerate(toks):
+                try:
+                    dtype(t)
+                except (ValueError, OverflowError):
+                    self.bad(f"{label(i)}: not a number: '{t}'")
+            raise
+
+    def header(self, names):
+        vals = self.numbers(self.take("header", len(names)), np.int64, lambda i: names[i])
+        for n, v in zip(names, vals):
+            if not 0 <= v <= 0xFFFFFFFF:
+                self.bad(f"header: {n} = {int(v)} is not a count (0 .. 4294967295)")
+        return [int(v) for v in vals]
+
+    def indices(self, name, toks, lowest=0):
+        vals = self.numbers(toks, np.int64, lambda i: f"{name}[{i}]")
+        bad = np.flatnonzero((vals < lowest) | (vals > 0xFFFFFFFF))
+        if bad.size:
+            self.bad(f"{name}[{int(bad[0])}] = {int(vals[bad[0]])} is not an index")
+        return (vals & 0xFFFFFFFF).astype(np.uint32)
+
+    def values(self, name, toks):
+        return self.numbers(toks, np.float64, lambda i: f"{name}[{i}]")
+
+    def checked(self, matrix, check):
+        try:
+            check(matrix)
+        except ValueError as e:
+            self.bad(str(e))
+        return matrix
 
 
 def read_dense(path, dtype=np.float32):
-    """`rows cols [nnz]` header (rest of the line ignored, dense.cu:23-24) then
-    one text line per row."""
-    with open(path, "r") as f:
-        head = f.readline().split()
+    """`rows cols [nnz]` header (rest of the line ignored, dense.cu:23-24) then one text line per row, each
+    of exactly `cols` numbers."""
+    t = _Text(path, "dense")
+    lines = t.text.split("\n")
+    head = lines[0].split()
+    try:
         rows, cols = int(head[0]), int(head[1])
-        data = np.empty((rows, cols), dtype=np.float64)
-        for i in range(rows):
-            data[i] = _tokens(f.readline(), cols, float)
+    except (IndexError, ValueError):
+        t.bad(f"header is not two numbers: '{lines[0].strip()}'")
+    if not (0 <= rows <= 0xFFFFFFFF and 0 <= cols <= 0xFFFFFFFF):
+        t.bad(f"header is not two counts: '{lines[0].strip()}'")
+    t.promise(2 + rows * cols)
+    data = np.empty((rows, cols), dtype=np.float64)
+    for i in range(rows):
+        toks = lines[1 + i].split() if 1 + i < len(lines) else None
+        if toks is None:
+            t.bad(f"fewer rows than the header says: row {i} is missing")
+        if len(toks) != cols:
+            t.bad(f"row {i} holds {len(toks)} tokens, {cols} are needed")
+        data[i] = t.numbers(toks, np.float64, lambda j: f"row {i}, token {j}")
     return Dense(data.astype(dtype))
 
 
 def read_csr(path, dtype=np.float32):
-    with open(path, "r") as f:
-        rows, cols, nnz = (int(x) for x in f.readline().split()[:3])
-        row_ptrs = _tokens(f.readline(), rows + 1, int)
-        col_idxs = _tokens(f.readline(), nnz, int)
-        data = _tokens(f.readline(), nnz, float)
-    return CSR(rows, cols, row_ptrs.astype(np.uint32), col_idxs.astype(np.uint32), data.astype(dtype))
+    t = _Text(path, ".csr")
+    rows, cols, nnz = t.header(("numRows", "numCols", "numNonZero"))
+    t.promise(3 + rows + 1 + 2 * nnz)
+    row_ptrs = t.indices("rowPtrs", t.take("rowPtrs", rows + 1))
+    col_idxs, data = t.indices("colIdxs", t.take("colIdxs", nnz)), t.values("data", t.take("data", nnz))
+    return t.checked(CSR(rows, cols, row_ptrs, col_idxs, data.astype(dtype)), check_csr)
 
 
 def read_coo(path, dtype=np.float32):
-    with open(path, "r") as f:
-        rows, cols, nnz = (int(x) for x in f.readline().split()[:3])
-        body = np.loadtxt(f, dtype=np.float64, ndmin=2) if nnz else np.zeros((0, 3))
-    if body.shape[0] != nnz:
-        raise ValueError(f"{path}: expected {nnz} entries, found {body.shape[0]}")
-    return COO(rows, cols, body[:, 0].astype(np.uint32), body[:, 1].astype(np.uint32), body[:, 2].astype(dtype))
+    t = _Text(path, ".coo")
+    rows, cols, nnz = t.header(("numRows", "numCols", "numNonZero"))
+    t.promise(3 + 3 * nnz)
+    toks = t.take("entries", 3 * nnz)                      # "row col value" per entry
+    r, c, v = t.indices("rowIdxs", toks[0::3]), t.indices("colIdxs", toks[1::3]), t.values("data", toks[2::3])
+    return t.checked(COO(rows, cols, r, c, v.astype(dtype)), check_coo)
 
 
 def read_bsr(path, dtype=np.float32):
-    with open(path, "r") as f:
-        rows, cols, nnz, br, bc, nblocks = (int(x) for x in f.readline().split()[:6])
-        ptrs = _tokens(f.readline(), rows // br + 1, int)
-        idxs = _tokens(f.readline(), nblocks, int)
-        vals = np.array(f.read().split(), dtype=np.float64)
-    if vals.shape[0] != nblocks * br * bc:
-        raise ValueError(f"{path}: expected {nblocks * br * bc} block values, found {vals.shape[0]}")
-    return BSR(rows, cols, nnz, br, bc, ptrs.astype(np.uint32), idxs.astype(np.uint32),
-               vals.reshape(nblocks, br, bc).astype(dtype))
+    t = _Text(path, ".bsr")
+    rows, cols, nnz, br, bc, nblocks = t.header(("numRows", "numCols", "numNonZero", "blockRowSize", "blockColSize", "numBlocks"))
+    if br == 0 or bc == 0:
+        t.bad(f"bsr check: block shape {br} x {bc} must be positive")
+    if rows % br:
+        t.bad(f"bsr check: M = {rows} is not a multiple of bR = {br}")
+    t.promise(6 + rows // br + 1 + nblocks + nblocks * br * bc)
+    ptrs = t.indices("blockRowPtrs", t.take("blockRowPtrs", rows // br + 1))
+    idxs = t.indices("blockColIdxs", t.take("blockColIdxs", nblocks))
+    vals = t.values("data", t.take("data", nblocks * br * bc))
+    return t.checked(BSR(rows, cols, nnz, br, bc, ptrs, idxs, vals.reshape(nblocks, br, bc).astype(dtype)), check_bsr)
 
 
 def _read_ell_pair(index_path, values_path, lines_from_cols, dtype):
-    with open(index_path, "r") as f:
-        rows, cols, nnz, width = (int(x) for x in f.readline().split()[:4])
-        n = cols if lines_from_cols else rows
-        idx = np.array(f.read().split(), dtype=np.int64)
-    with open(values_path, "r") as f:
-        val = np.array(f.read().split(), dtype=np.float64)
-    if idx.shape[0] != n * width or val.shape[0] != n * width:
-        raise ValueError(f"{index_path}: expected {n * width} ELL slots")
-    # "-1" -> 0xFFFFFFFF exactly as `istream >> uint32_t` wraps it (sparse_ell.cu:38-43)
-    return rows, cols, nnz, width, (idx & 0xFFFFFFFF).astype(np.uint32).reshape(n, width), \
-        val.reshape(n, width).astype(dtype)
+    t = _Text(index_path, "ELL")
+    rows, cols, nnz, width = t.header(("numRows", "numCols", "numNonZero", "width"))
+    n = cols if lines_from_cols else rows
+    t.promise(4 + n * width)
+    # "-1" -> 0xFFFFFFFF exactly as `istream >> uint32_t` wraps it (sparse_ell.cu:38-43); what a wrapped negative
+    # means (padding or not) is the layout's business: check_ell
+    name = "rowIdxs" if lines_from_cols else "colIdxs"
+    idx = t.indices(name, t.take(name, n * width), lowest=-0x80000000)
+    tv = _Text(values_path, "ELL")
+    tv.promise(n * width)
+    val = tv.values("data", tv.take("data", n * width))
+    return t, rows, cols, nnz, width, idx.reshape(n, width), val.reshape(n, width).astype(dtype)
 
 
 def read_ell_colmajor(rowind_path, values_path, dtype=np.float32):
-    rows, cols, nnz, w, idx, val = _read_ell_pair(rowind_path, values_path, True, dtype)
-    return ELLColMajor(rows, cols, nnz, w, idx, val)
+    t, rows, cols, nnz, w, idx, val = _read_ell_pair(rowind_path, values_path, True, dtype)
+    return t.checked(ELLColMajor(rows, cols, nnz, w, idx, val), check_ell)
 
 
 def read_ell_rowmajor(colind_path, values_path, dtype=np.float32):
-    rows, cols, nnz, w, idx, val = _read_ell_pair(colind_path, values_path, False, dtype)
-    return ELLRowMajor(rows, cols, nnz, w, idx, val)
+    t, rows, cols, nnz, w, idx, val = _read_ell_pair(colind_path, values_path, False, dtype)
+    return t.checked(ELLRowMajor(rows, cols, nnz, w, idx, val), check_ell)
 
 
 # --------------------------------------------------------------------------

@@ -150,6 +150,7 @@ class MultiEllSpmm(_MultiBase):
 
     def __init__(self, ell, n_cols, devices, gather="first", kernel=0, acc="reference", ldc=None):
         from . import formats
+        ops.check_host(ell)      # this class uploads the index arrays itself: the structure check every from_host runs
         if isinstance(ell, formats.ELLColMajor):
             ell = ops.colmajor_ell_to_rowmajor(ell)
         self.kernel, self.acc, self.width = int(kernel), capi.ACC_MODES[acc], int(ell.width)

@@ -45,6 +45,39 @@ def _require_gpu(*tensors):
             raise ValueError("mispmm ops take device tensors; there is no CPU path")
 
 
+def check_host(m):
+    """The validity contract of include/mispmm.h on a host container, by the library's own checker (mispmm_csr_check_host /
+    _coo_ / _ell_ / _bsr_): raises capi.MispmmError naming the first defect.  Every from_host runs it before anything is
+    built or uploaded; an index array that is not uint32 is range-checked first (ValueError), never wrapped."""
+    l, u32 = capi.lib(), formats.as_u32
+    if isinstance(m, formats.CSR):
+        rp, ci = u32("rowPtrs", m.row_ptrs), u32("colIdxs", m.col_idxs)
+        st = l.mispmm_csr_check_host(m.num_rows, m.num_cols, m.nnz, rp.ctypes.data, rp.size, ci.ctypes.data, ci.size)
+        values, want = m.data, m.nnz
+    elif isinstance(m, formats.COO):
+        ri, ci = u32("rowIdxs", m.row_idxs), u32("colIdxs", m.col_idxs)
+        st = l.mispmm_coo_check_host(m.num_rows, m.num_cols, m.nnz, ri.ctypes.data, ri.size, ci.ctypes.data, ci.size)
+        values, want = m.data, m.nnz
+    elif isinstance(m, formats.ELLColMajor):
+        ri = u32("rowIdxs", m.row_idxs)
+        st = l.mispmm_ell_check_host(capi.ELL_COLUMN_MAJOR, m.num_rows, m.num_cols, m.max_col_nnz, ri.ctypes.data, ri.size)
+        values, want = m.data, ri.size
+    elif isinstance(m, formats.ELLRowMajor):
+        ci = u32("colIdxs", m.col_idxs)
+        st = l.mispmm_ell_check_host(capi.ELL_ROW_MAJOR, m.num_rows, m.num_cols, m.width, ci.ctypes.data, ci.size)
+        values, want = m.data, ci.size
+    elif isinstance(m, formats.BSR):
+        rp, ci = u32("blockRowPtrs", m.block_row_ptrs), u32("blockColIdxs", m.block_col_idxs)
+        st = l.mispmm_bsr_check_host(m.num_rows, m.num_cols, m.block_row_size, m.block_col_size, m.num_blocks, rp.ctypes.data, rp.size,
+                                     ci.ctypes.data, ci.size, np.asarray(m.data).size)
+        values, want = m.data, np.asarray(m.data).size
+    else:
+        raise TypeError(f"no structure check for {type(m).__name__}")
+    capi.check(st)
+    if np.asarray(values).size != want:
+        raise ValueError(f"{type(m).__name__}: data holds {np.asarray(values).size} values, {want} are needed")
+
+
 def _dense_ld(t):
     if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 and t.shape[1] > 1:
         raise ValueError("dense operands must be 2-D float32 with unit column stride")
@@ -203,13 +236,16 @@ class DeviceCSR:
     tuned: dict = field(default_factory=dict)   # (n, acc) -> (use the plan?, (storage-order us, plan-order us)) as measured by use_plan
 
     @staticmethod
-    def from_host(csr, device="cuda", spans=None, share_len=0, plan=None, dtype=torch.float32):
+    def from_host(csr, device="cuda", spans=None, share_len=0, plan=None, dtype=torch.float32, check=True):
         """spans: True / False to build the span list of the split kernel or not; None = when the mean row holds 24 entries
         or more (where the library's kernel 0 takes the split kernel).  share_len: rows longer than this are dealt to the 4
         waves of a workgroup (0 = the library's default, 128).  plan: True / False to keep a clustered row order or not;
         None = when the matrix has short rows (no span list), at least 1024 rows, and the clustering cuts the distinct
         columns per row part by PLAN_MIN_GAIN or more (a once-per-upload analysis like the two above).
-        dtype=torch.float64: the host array's own values in double, for mispmm_csr_f64; no span list, no plan."""
+        dtype=torch.float64: the host array's own values in double, for mispmm_csr_f64; no span list, no plan.
+        check: run check_host first (one pass over the index arrays); False only for arrays already checked."""
+        if check:
+            check_host(csr)
         if _check_dtype(dtype):
             return DeviceCSR(csr.num_rows, csr.num_cols, csr.nnz, _dev_u32(csr.row_ptrs, device), _dev_u32(csr.col_idxs, device),
                              _dev_f64(csr.data, device))
@@ -240,10 +276,12 @@ class DeviceELL:
     compact: tuple = None     # (nnz, rowPtrs, colIdxs, vals) of the occupied slots, when most of the ELL is padding
 
     @staticmethod
-    def from_host(ell, device="cuda", compact=None, dtype=torch.float32):
+    def from_host(ell, device="cuda", compact=None, dtype=torch.float32, check=True):
         """compact: True / False to list the occupied slots (mispmm_ell_compact_host) or not; None = when more than half of
         the slots are padding.  dtype=torch.float64: the occupied slots as a row list of doubles in spmmELLCpu's order of
-        addition (compact = that list, col_idxs / data its arrays), for mispmm_csr_f64."""
+        addition (compact = that list, col_idxs / data its arrays), for mispmm_csr_f64.  check: run check_host first."""
+        if check:
+            check_host(ell)
         if _check_dtype(dtype):
             rp, ci, va = ell_rows_f64(ell)
             listed = (int(rp[-1]), _dev_u32(rp, device), _dev_u32(ci, device), _dev_f64(va, device), None)
@@ -279,7 +317,9 @@ class DeviceBSR:
     data: torch.Tensor       # float32 blocks, or int16-viewed bf16 bit patterns
 
     @staticmethod
-    def from_host(bsr, device="cuda"):
+    def from_host(bsr, device="cuda", check=True):
+        if check:
+            check_host(bsr)
         return DeviceBSR(bsr.num_rows, bsr.num_cols, bsr.block_row_size, bsr.block_col_size, bsr.num_blocks,
                          _dev_u32(bsr.block_row_ptrs, device), _dev_u32(bsr.block_col_idxs, device),
                          _dev_f32(bsr.data.reshape(-1), device))
@@ -336,10 +376,12 @@ class DeviceCOO:
     row_bounds: torch.Tensor = None   # float64 only: the (M+1) row boundaries of the sorted entries (mispmm_coo_row_bounds)
 
     @staticmethod
-    def from_host(coo, device="cuda", dtype=torch.float32):
+    def from_host(coo, device="cuda", dtype=torch.float32, check=True):
         """Entries sorted by row only, a row's entries in storage order: the reference (spmm_coo.cpp) adds them into the row
         in that order, so sorting them by column as well would change the fp32 sums.  dtype=torch.float64: the values in
-        double and the row boundaries built once here, for mispmm_csr_f64; no span list."""
+        double and the row boundaries built once here, for mispmm_csr_f64; no span list.  check: run check_host first."""
+        if check:
+            check_host(coo)
         f64 = _check_dtype(dtype)
         order = np.argsort(np.asarray(coo.row_idxs), kind="stable")
         rows = np.asarray(coo.row_idxs)[order]
@@ -580,7 +622,9 @@ class DeviceCSRTiles:
     row_map: torch.Tensor        # plan position -> C row
 
     @staticmethod
-    def from_host(csr, device="cuda", max_rows=16, max_cols=128):
+    def from_host(csr, device="cuda", max_rows=16, max_cols=128, check=True):
+        if check:
+            check_host(csr)
         w = uniform_row_nnz(csr.row_ptrs)
         if w == 0 or w > 16:
             raise ValueError("LDS tiles take rows of one width of 1..16 entries")
@@ -627,8 +671,10 @@ class DeviceCSRPanels:
     panel_ptrs: torch.Tensor     # num_rows x (num_panels + 1) offsets into col_idxs / data, row-major
 
     @staticmethod
-    def from_host(csr, device="cuda", panel_rows=None):
+    def from_host(csr, device="cuda", panel_rows=None, check=True):
         """Raises capi.MispmmError for a matrix the builder declines (a row whose columns do not ascend: ERR_UNSUPPORTED)."""
+        if check:
+            check_host(csr)
         l = capi.lib()
         depth = int(panel_rows) if panel_rows is not None else l.mispmm_csr_panel_rows()
         rp = np.ascontiguousarray(csr.row_ptrs, dtype=np.uint32)
@@ -692,10 +738,13 @@ def spmm_bsr(a, b, out=None, kernel=0, acc="reference", stream=None):
     return c
 
 
-def bsr_nonzeros(bsr, device="cuda", dtype=torch.float32):
+def bsr_nonzeros(bsr, device="cuda", dtype=torch.float32, check=True):
     """The non-zero block entries of a host BSR as a DeviceCSR in the reference's order of addition
     (mispmm_bsr_nonzeros_host) -- the once-per-upload analysis step of the zero-skipping BSR path.  dtype=torch.float64:
-    the values in double (mispmm_bsr_nonzeros_f64_host), for mispmm_csr_f64; no span list."""
+    the values in double (mispmm_bsr_nonzeros_f64_host), for mispmm_csr_f64; no span list.  check: run check_host first -- the
+    builders themselves cannot (their signatures carry no K)."""
+    if check:
+        check_host(bsr)
     if _check_dtype(dtype):
         rp, ci, va = bsr_nonzeros_f64_host(bsr)
         return DeviceCSR(bsr.num_rows, bsr.num_cols, int(rp[-1]), _dev_u32(rp, device), _dev_u32(ci, device), _dev_f64(va, device))
@@ -1064,7 +1113,9 @@ class DeviceBSRC:
     tiles: torch.Tensor      # int16 view of bf16 bits, [num_steps, 16, 32]
 
     @staticmethod
-    def from_host(bsr, device="cuda"):
+    def from_host(bsr, device="cuda", check=True):
+        if check:
+            check_host(bsr)
         l = capi.lib()
         ptrs = np.ascontiguousarray(bsr.block_row_ptrs, dtype=np.uint32)
         cols = np.ascontiguousarray(bsr.block_col_idxs, dtype=np.uint32)
@@ -1106,7 +1157,9 @@ class DeviceBSRCSlots:
     tiles: torch.Tensor      # int16 view of bf16 bits, [num_steps, 16, 32]
 
     @staticmethod
-    def from_host(bsr, device="cuda"):
+    def from_host(bsr, device="cuda", check=True):
+        if check:
+            check_host(bsr)
         l = capi.lib()
         ptrs = np.ascontiguousarray(bsr.block_row_ptrs, dtype=np.uint32)
         cols = np.ascontiguousarray(bsr.block_col_idxs, dtype=np.uint32)

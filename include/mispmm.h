@@ -763,6 +763,41 @@ int mispmm_multi_bsrc_slots_bf16(uint32_t ndev, const int *devices, const mispmm
  * opened by a one-process-per-GPU host: mispmm/dist.py).  Enqueue only; capturable into a graph. */
 int mispmm_slab_scatter(mispmm_stream_t stream, const void *src, size_t bytes, void *const *dsts_host, uint32_t ndst);
 
+/* ------------------------------------------------------- validity of a sparse structure */
+/* THE CONTRACT.  Every kernel of this library trusts its index arrays: it reads B, C and the value arrays at the positions
+ * they name without a bounds test.  A structure may therefore be handed to a compute call or to a `_host` builder only when
+ * it is VALID, and it is valid when, and only when, the conditions below hold -- what memory safety needs, nothing more.
+ *   CSR   rowPtrs has M + 1 entries, rowPtrs[0] == 0, rowPtrs never decreases, rowPtrs[M] == nnz; colIdxs has nnz entries,
+ *         each below K.  (So M == 0 or K == 0 goes with nnz == 0 only.)
+ *   COO   rowIdxs and colIdxs (and the values) have nnz entries; each row index is below M, each column index below K.
+ *         Any order of the entries is valid.
+ *   ELL, column-major (the reference's pair of files): K * maxColNnz slots; a row index with the sign bit set is padding
+ *         (the reference's `if (row >= 0)`, src/spmm/ell/spmm_ell.cpp:21); any other is below M.
+ *   ELL, row-major: M * width slots; padding is exactly 0xFFFFFFFF, the one value the kernels drop; any other column index
+ *         is below K (0xFFFFFFFE is therefore invalid).
+ *   BSR   bR > 0 and bC > 0, M % bR == 0 and K % bC == 0; blockRowPtrs has M / bR + 1 entries, starts at 0, never
+ *         decreases and ends at numBlocks; blockColIdxs has numBlocks entries, each below K / bC; the data holds
+ *         numBlocks * bR * bC values.
+ *   Dense text file: a header `rows cols` followed by exactly `cols` numeric tokens on each of `rows` lines.
+ * NOT required, and accepted everywhere: columns of a row in any order, repeated (row, column) pairs, explicit zeros, NaN and
+ * Inf values, empty rows, empty block rows, block columns in any order or repeated, ELL rows that are all padding, nnz == 0.
+ *
+ * The checkers below test exactly these conditions on HOST arrays in one pass; they launch nothing.  Every `num*` argument is
+ * the number of entries the array really holds, so the length conditions are tested and not assumed.  MISPMM_OK, or
+ * MISPMM_ERR_INVALID_ARG with mispmm_last_error() naming the first defect: which array, which position, the value, the bound.
+ * The text readers and every copy2Device() of the C++ host layer, and every from_host of the Python layer, call them before
+ * anything is uploaded or built. */
+enum mispmm_ell_layout { MISPMM_ELL_COLUMN_MAJOR = 0, MISPMM_ELL_ROW_MAJOR = 1 };
+int mispmm_csr_check_host(uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowPtrs_host, uint64_t numRowPtrs,
+                          const uint32_t *colIdxs_host, uint64_t numColIdxs);
+int mispmm_coo_check_host(uint32_t M, uint32_t K, uint32_t nnz, const uint32_t *rowIdxs_host, uint64_t numRowIdxs,
+                          const uint32_t *colIdxs_host, uint64_t numColIdxs);
+/* column-major: idxs_host = row indices, K * width slots (width = maxColNnz); row-major: column indices, M * width slots */
+int mispmm_ell_check_host(int layout, uint32_t M, uint32_t K, uint32_t width, const uint32_t *idxs_host, uint64_t numIdxs);
+int mispmm_bsr_check_host(uint32_t M, uint32_t K, uint32_t bR, uint32_t bC, uint32_t numBlocks, const uint32_t *blockRowPtrs_host,
+                          uint64_t numBlockRowPtrs, const uint32_t *blockColIdxs_host, uint64_t numBlockColIdxs,
+                          uint64_t numValues);
+
 #ifdef __cplusplus
 }
 #endif
