@@ -19,7 +19,10 @@ With z, lse, P = exp(z - lse), dP = <dO, V>, delta = <dO, O>, dS = scale P (dP -
     E_dS     scale (E_P X + P (E_dP + E_delta)) + (4 u + r8) scale (P + E_P) X + 2^-126,  X = |dP - delta| + E_dP + E_delta
              four fp32 roundings (the difference, two products, the fp32 scale), then one rounding to bf16
     dQ       sum_key E_dS |K| + g_L sum (|dS| + E_dS) |K|,  L the keys of the row;  dK, dV: the same over the rows that store the
-             key, dV with P (+ sum P E_g |.| where grad_out was rounded); a bf16 gradient: + r8 (|exact| + tolerance)."""
+             key, dV with P (+ sum P E_g |.| where grad_out was rounded); a bf16 gradient: + r8 (|exact| + tolerance).
+
+forward_f32, delta_f32, _weights and backward_f32 take `fault=`: a name of tests/_attn_mutants.py, a deliberate breach of the header
+put into THIS code and not a copy of it, for tests/test_attn_mutants_cpu.py; None (the default) is the algorithm and keeps its bits."""
 import functools
 import itertools
 
@@ -27,6 +30,8 @@ import numpy as np
 
 from mispmm import formats, ops
 
+import _attn_mutants
+from _attn_fused_ref import _exp32, bf16_trunc, fused_rows, mfma_add
 from _sddmm_bsr_ref import bound as sddmm_bsr_bound, full_mantissa as bf16_full_mantissa
 from _softmax_bsr_ref import bf16_round, fma32, fwd_bound, pattern
 
@@ -280,11 +285,6 @@ def chain_grad_tolerances(name, q, k, v, g, scale, mask):
 
 
 # ---- the algorithm as built, numpy float32
-def _exp32(t):
-    """v_exp_f32 of fl(t * log2 e), in numpy float32."""
-    return np.exp2((t.astype(np.float32) * np.float32(1.44269504088896340736)).astype(np.float32))
-
-
 def _block_rows(bsr):
     ptrs = np.asarray(bsr.block_row_ptrs, dtype=np.int64)
     cols = np.asarray(bsr.block_col_idxs, dtype=np.int64)
@@ -293,81 +293,61 @@ def _block_rows(bsr):
         yield r, lo, hi, (cols[lo:hi, None] * bs + np.arange(bs)).reshape(-1)
 
 
-def forward_f32(name, q, k, v, mask, scale):
-    """tests/_attn_fused_ref.py::fused_f32 on any of the six patterns: (out [M, Dv], lse [M]) of one head, numpy float32."""
-    f32 = np.float32
-    bsr = bwd_pattern(name)[0]
-    bs = bsr.block_row_size
-    out, lse = np.zeros((bsr.num_rows, v.shape[1]), f32), np.full(bsr.num_rows, -np.inf, f32)
-    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        for r, lo, hi, keys in _block_rows(bsr):
-            if hi == lo:
-                continue
-            rows = slice(r * bs, (r + 1) * bs)
-            s = (q[rows].astype(np.float64) @ k[keys].T.astype(np.float64)).astype(f32)
-            z = f32(scale) * s if mask is None else fma32(f32(scale), s, mask[lo:hi].transpose(1, 0, 2).reshape(bs, -1))
-            vk = v[keys].astype(np.float64)
-            pad = -keys.shape[0] % 32
-            z = np.concatenate([z, np.full((bs, pad), -np.inf, f32)], axis=1)
-            vk = np.concatenate([vk, np.zeros((pad, v.shape[1]))], axis=0)
-            m, mu = np.full(bs, -np.inf, f32), np.zeros(bs, f32)
-            l, lx = np.zeros((bs, 4), f32), np.zeros((bs, 4), f32)
-            o = np.zeros((bs, v.shape[1]), f32)
-            lanes = lambda x: x.reshape(bs, 2, 4, 4).transpose(0, 2, 1, 3).reshape(bs, 4, 8)   # noqa: E731
-            for at in range(0, z.shape[1], 32):
-                zs = z[:, at:at + 32]
-                m_new = np.fmax(m, np.fmax.reduce(zs, axis=1))
-                mu_new = np.where(np.isinf(m_new), f32(0), m_new)
-                alpha = np.where(np.isneginf(m), f32(1), _exp32(mu - mu_new))
-                m, mu = m_new, mu_new
-                w = _exp32(zs - mu[:, None])
-                wb = bf16_round(w)
-                t, tx = np.zeros((bs, 4), f32), np.zeros((bs, 4), f32)
-                for j in range(8):
-                    t = t + lanes(wb)[:, :, j]
-                    tx = tx + lanes(w)[:, :, j]
-                l = l * alpha[:, None] + t
-                lx = lx * alpha[:, None] + tx
-                o = ((o * alpha[:, None]).astype(np.float64) + wb.astype(np.float64) @ vk[at:at + 32]).astype(f32)
-            meet = lambda x: (x[:, 0] + x[:, 1]) + (x[:, 2] + x[:, 3])        # noqa: E731
-            out[rows] = o * (f32(1) / meet(l))[:, None]
-            lse[rows] = mu + np.log(meet(lx)).astype(f32)
-    return out, lse
+def forward_f32(name, q, k, v, mask, scale, fault=None):
+    """tests/_attn_fused_ref.py::fused_f32 on any of the six patterns: (out [M, Dv], lse [M]) of one head, numpy float32 -- one
+    body, fused_rows, behind both."""
+    return fused_rows(bwd_pattern(name)[0], q, k, v, mask, scale, fault)
 
 
-def delta_f32(g, out):
+def delta_f32(g, out, fault=None):
     """delta as the row pass forms it: lane gq of a row sums columns 32 s + 8 gq .. + 7 of every 32-column step s ascending by fma,
     the four lanes meet as (g0 + g1) + (g2 + g3).  out: float32 (a bf16 out widened exactly)."""
+    _attn_mutants.check(fault, _attn_mutants.BACKWARD)
     f32 = np.float32
+    if fault == "delta_from_bf16_out":
+        out = bf16_round(out)
     rows, dv = g.shape
     lane = np.zeros((rows, 4), f32)
     for s in range(0, dv, 32):
         for gq in range(4):
             for c in range(s + 8 * gq, min(s + 8 * gq + 8, dv)):
                 lane[:, gq] = fma32(g[:, c], out[:, c], lane[:, gq])
-    return (lane[:, 0] + lane[:, 1]) + (lane[:, 2] + lane[:, 3])
+    delta = (lane[:, 0] + lane[:, 1]) + (lane[:, 2] + lane[:, 3])
+    return delta * f32(1 + 2.0 ** -9) if fault == "delta_scaled" else delta
 
 
-def _weights(z, dp, lse, delta, scale):
+def _weights(z, dp, lse, delta, scale, fault=None):
     """(bf16 P, bf16 dS) as float32 arrays; lse, delta broadcast against z."""
+    _attn_mutants.check(fault, _attn_mutants.BACKWARD)
     f32 = np.float32
+    if fault == "lse_shifted":
+        lse = lse + f32(2.0 ** -9)
     with np.errstate(invalid="ignore", over="ignore"):
-        p = _exp32(z - lse)
-        ds = (p * (dp - delta).astype(f32)).astype(f32) * f32(scale)
-    return bf16_round(p), bf16_round(ds)
+        p = _exp32(z - lse, fault)
+        pin = bf16_round(p) if fault == "p_bf16_before_ds" else p
+        ds = (pin * (dp - delta).astype(f32)).astype(f32) * f32(scale)
+    return (bf16_trunc(p) if fault == "p_truncated" else bf16_round(p)), (bf16_trunc(ds) if fault == "ds_truncated" else bf16_round(ds))
 
 
-def backward_f32(name, q, k, v, g, out, lse, mask, scale, grads_bf16):
+def backward_f32(name, q, k, v, g, out, lse, mask, scale, grads_bf16, fault=None):
     """(dq, dk, dv) of one head by the two passes as built, in numpy float32: 32-key resp. 32-query steps in storage order, P and
     dS rounded to bf16 before the second products, fp32 accumulators from +0.  The sum inside an MFMA is taken in float64 and
-    rounded once (the order inside the instruction is its own).  out, lse: what the forward stored (float32 arrays)."""
+    rounded once (the order inside the instruction is its own).  out, lse: what the forward stored (float32 arrays).  g: grad_out;
+    a float32 one is rounded to bf16 here, as the Python layer does before the call (one that holds bf16 numbers keeps its bits).
+    fault: a name of tests/_attn_mutants.py (BACKWARD or HONEST); None: the algorithm."""
+    _attn_mutants.check(fault, _attn_mutants.BACKWARD)
     f32, f64 = np.float32, np.float64
     a, at, perm = bwd_pattern(name)
     bs = a.block_row_size
-    delta = delta_f32(g, out)
+    if fault != "grad_out_unrounded":
+        g = bf16_round(g)
+    if fault == "bwd_scale_bf16":
+        scale = bf16_round(f32(scale))
+    delta = delta_f32(g, out, fault)
     dq = np.zeros((a.num_rows, q.shape[1]), f32)
     dk = np.zeros((a.num_cols, q.shape[1]), f32)
     dv = np.zeros((a.num_cols, v.shape[1]), f32)
+    acc = np.zeros((bs, q.shape[1]), f32)
     for r, lo, hi, keys in _block_rows(a):
         if hi == lo:
             continue
@@ -375,24 +355,32 @@ def backward_f32(name, q, k, v, g, out, lse, mask, scale, grads_bf16):
         s = (q[rows].astype(f64) @ k[keys].T.astype(f64)).astype(f32)
         z = f32(scale) * s if mask is None else fma32(f32(scale), s, mask[lo:hi].transpose(1, 0, 2).reshape(bs, -1))
         dp = (g[rows].astype(f64) @ v[keys].T.astype(f64)).astype(f32)
-        _, dsb = _weights(z, dp, lse[rows, None], delta[rows, None], scale)
-        acc = np.zeros((bs, q.shape[1]), f32)
+        _, dsb = _weights(z, dp, lse[rows, None], delta[rows, None], scale, fault)
+        if fault != "dq_acc_carried":
+            acc = np.zeros((bs, q.shape[1]), f32)
         for c in range(0, keys.shape[0], 32):
-            acc = (acc.astype(f64) + dsb[:, c:c + 32].astype(f64) @ k[keys[c:c + 32]].astype(f64)).astype(f32)
+            acc = mfma_add(acc, dsb[:, c:c + 32], k[keys[c:c + 32]], fault)
         dq[rows] = acc
     for c, lo, hi, qs in _block_rows(at):
         if hi == lo:
             continue
         keys = slice(c * bs, (c + 1) * bs)
         s = (q[qs].astype(f64) @ k[keys].T.astype(f64)).astype(f32)                          # [queries, keys]
-        z = f32(scale) * s if mask is None else fma32(f32(scale), s, mask[perm[lo:hi].astype(np.int64)].reshape(-1, bs))
+        if mask is None:
+            z = f32(scale) * s
+        else:
+            blocks = mask[perm[lo:hi].astype(np.int64)]
+            z = fma32(f32(scale), s, (blocks.transpose(0, 2, 1) if fault == "mask_transposed_cols" else blocks).reshape(-1, bs))
         dp = (g[qs].astype(f64) @ v[keys].T.astype(f64)).astype(f32)
-        pb, dsb = _weights(z, dp, lse[qs, None], delta[qs, None], scale)
+        pb, dsb = _weights(z, dp, lse[qs, None], delta[qs, None], scale, fault)
+        if fault == "last_query_dropped":
+            pb, dsb = pb.copy(), dsb.copy()
+            pb[-1], dsb[-1] = 0, 0
         acck, accv = np.zeros((bs, q.shape[1]), f32), np.zeros((bs, v.shape[1]), f32)
         for at_ in range(0, qs.shape[0], 32):
             step = qs[at_:at_ + 32]
-            acck = (acck.astype(f64) + dsb[at_:at_ + 32].T.astype(f64) @ q[step].astype(f64)).astype(f32)
-            accv = (accv.astype(f64) + pb[at_:at_ + 32].T.astype(f64) @ g[step].astype(f64)).astype(f32)
+            acck = mfma_add(acck, dsb[at_:at_ + 32].T, q[step], fault)
+            accv = mfma_add(accv, pb[at_:at_ + 32].T, g[step], fault)
         dk[keys], dv[keys] = acck, accv
     if grads_bf16:
         dq, dk, dv = bf16_round(dq), bf16_round(dk), bf16_round(dv)

@@ -13,12 +13,16 @@ E_z: the largest error of a z of the row -- the SDDMM bound of mispmm.h through 
 fma's rounding, exactly as _attention_tolerances forms it (logsumexp moves by at most the largest change of an argument); the
 second term bounds the relative error of the fp32 sum of exponentials (header of mispmm_attn.h: every term passes at most
 L / 16 + 11 roundings, (3 T + 2) u for its exponential, (3 T + L / 16) u for the chain of rescale factors); the third is logf to
-an ulp and the final addition.  1.01 covers second-order terms, as in _attention_tolerances."""
+an ulp and the final addition.  1.01 covers second-order terms, as in _attention_tolerances.
+
+fused_rows / fused_f32 take `fault=`: a name of tests/_attn_mutants.py, a deliberate breach of the header put into THIS code and
+not a copy of it, for tests/test_attn_mutants_cpu.py; None (the default) is the algorithm and keeps its bits."""
 import functools
 import itertools
 
 import numpy as np
 
+import _attn_mutants
 from _sddmm_bsr_ref import bound as sddmm_bsr_bound, full_mantissa as bf16_full_mantissa
 from _softmax_bsr_ref import bf16_round, causal_mask, fma32, pattern
 
@@ -104,24 +108,47 @@ def lse_reference(name, q, k, mask, scale):
     return exact, tol
 
 
-def _exp32(t):
+def _exp32(t, fault=None):
     """v_exp_f32 of fl(t * log2 e), in numpy float32."""
+    if fault == "exp_float64":
+        return np.exp(t.astype(np.float32).astype(np.float64)).astype(np.float32)
     return np.exp2((t.astype(np.float32) * np.float32(1.44269504088896340736)).astype(np.float32))
 
 
-def fused_f32(name, q, k, v, mask, scale):
-    """(out [M, Dv], lse [M]) of one head by the algorithm as built, in numpy float32.  The MFMA sums are taken in float64 and
-    rounded once (the order inside the instruction is its own)."""
+def bf16_trunc(v):
+    """float32 -> the bf16 number next towards zero, as float32 (a fault: the contract rounds to nearest even)."""
+    return (np.ascontiguousarray(v, dtype=np.float32).view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
+
+
+def mfma_add(acc, a, b, fault=None):
+    """fl32(acc + a @ b) of an fp32 accumulator [m, n] and bf16 numbers a [m, k], b [k, n]: the sum taken in float64 and rounded once
+    (the order inside the instruction is its own); `mfma_fp32_sequential`: in fp32, term after term."""
+    if fault == "mfma_fp32_sequential":
+        acc, a, b = acc.astype(np.float32), a.astype(np.float32), b.astype(np.float32)
+        for j in range(a.shape[1]):
+            acc = acc + a[:, j:j + 1] * b[j][None, :]           # a product of two bf16 numbers is exact in fp32
+        return acc
+    return (acc.astype(np.float64) + a.astype(np.float64) @ b.astype(np.float64)).astype(np.float32)
+
+
+def fused_rows(bsr, q, k, v, mask, scale, fault=None):
+    """(out [M, Dv], lse [M]) of one head on the pattern `bsr` by the algorithm as built, in numpy float32.  The MFMA sums are taken
+    in float64 and rounded once (the order inside the instruction is its own).  fault: a name of tests/_attn_mutants.py (FORWARD or
+    HONEST); None: the algorithm."""
+    _attn_mutants.check(fault, _attn_mutants.FORWARD)
     f32 = np.float32
-    bsr = pattern(name)
     bs = bsr.block_row_size
     out, lse = np.zeros((bsr.num_rows, v.shape[1]), f32), np.full(bsr.num_rows, -np.inf, f32)
+    if fault == "scale_bf16":
+        scale = bf16_round(f32(scale))
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         for r, lo, hi, keys in _block_rows(bsr):
             if hi == lo:
                 continue
             rows = slice(r * bs, (r + 1) * bs)
             s = (q[rows].astype(np.float64) @ k[keys].T.astype(np.float64)).astype(f32)
+            if fault == "s_bf16":
+                s = bf16_round(s)
             z = f32(scale) * s if mask is None else fma32(f32(scale), s, _row_mask(mask, lo, hi, bs))
             vk = v[keys].astype(np.float64)
             pad = -keys.shape[0] % 32                         # 16 x 16, an odd block count: a half step, scores -Inf, V zeros
@@ -134,24 +161,38 @@ def fused_f32(name, q, k, v, mask, scale):
             for at in range(0, z.shape[1], 32):
                 zs = z[:, at:at + 32]
                 m_new = np.fmax(m, np.fmax.reduce(zs, axis=1))                # fmax drops a NaN
+                if fault == "stale_max" and at > 0:
+                    m_new = m
                 mu_new = np.where(np.isinf(m_new), f32(0), m_new)
-                alpha = np.where(np.isneginf(m), f32(1), _exp32(mu - mu_new))
+                alpha = np.where(np.isneginf(m), f32(1), _exp32(mu - mu_new, fault))
                 m, mu = m_new, mu_new
-                w = _exp32(zs - mu[:, None])
-                wb = bf16_round(w)
+                w = _exp32(zs - mu[:, None], fault)
+                if fault == "last_key_dropped" and at + 32 >= z.shape[1]:
+                    live = np.isfinite(zs)
+                    last = 31 - np.argmax(live[:, ::-1], axis=1)
+                    w = w.copy()
+                    w[live.any(axis=1), last[live.any(axis=1)]] = 0
+                wb = bf16_trunc(w) if fault == "w_truncated" else bf16_round(w)
                 # lane g of a row: keys 4g .. 4g + 3 of the first 16-key tile, then of the second, summed in that order
                 lanes = lambda x: x.reshape(bs, 2, 4, 4).transpose(0, 2, 1, 3).reshape(bs, 4, 8)   # noqa: E731
                 t, tx = np.zeros((bs, 4), f32), np.zeros((bs, 4), f32)
                 for j in range(8):
-                    t = t + lanes(wb)[:, :, j]
+                    t = t + lanes(w if fault == "divisor_unrounded" else wb)[:, :, j]
                     tx = tx + lanes(w)[:, :, j]
-                l = l * alpha[:, None] + t
+                l = l + t if fault == "rescale_skips_divisor" and at == 32 else l * alpha[:, None] + t
                 lx = lx * alpha[:, None] + tx
-                o = ((o * alpha[:, None]).astype(np.float64) + wb.astype(np.float64) @ vk[at:at + 32]).astype(f32)
+                o = mfma_add(o * alpha[:, None], wb, vk[at:at + 32], fault)
+                if fault == "acc_bf16":
+                    o = bf16_round(o)
             meet = lambda x: (x[:, 0] + x[:, 1]) + (x[:, 2] + x[:, 3])        # noqa: E731
             out[rows] = o * (f32(1) / meet(l))[:, None]
-            lse[rows] = mu + np.log(meet(lx)).astype(f32)
+            lse[rows] = mu + np.log(meet(l if fault == "lse_from_rounded" else lx)).astype(f32)
     return out, lse
+
+
+def fused_f32(name, q, k, v, mask, scale, fault=None):
+    """fused_rows on pattern(name)."""
+    return fused_rows(pattern(name), q, k, v, mask, scale, fault)
 
 
 def out_tolerance(name, q, k, v, scale, mask, out_bf16):

@@ -1,12 +1,11 @@
 """The fused block-sparse attention forward (mispmm_attn_bsr_bf16, ops.attention_bsr_bf16, block_sparse_attention(fused=True))
 on the GPU.  References and tolerances: tests/_attn_fused_ref.py -- out against float64 dense masked attention inside the `out`
 component of the three-launch chain's composed tolerance (no term added), lse against float64 logsumexp inside
-1.01 (E_z + (L + 8 T + 16) u + 2 u (|lse| + ln L + 1)).
+1.01 (E_z + (L + 8 T + 16) u + 2 u (|lse| + ln L + 1)).  The numerical checks are the functions of tests/_attn_checks.py, which
+tests/test_attn_mutants_cpu.py runs deliberately faulty restatements through; the tighter, derived check: tests/test_gpu_attn_tight.py.
 
 Worst |err| / tolerance printed on an MI355X (`-s` prints every one): out fp32 0.428, bf16 0.483;
 lse 0.040; a constant V 0.045 of (L + 16) 2^-24; ACTIVSg10K against the three-launch chain 0.425 of the two tolerances' sum."""
-import functools
-
 import numpy as np
 import pytest
 
@@ -14,10 +13,12 @@ torch = pytest.importorskip("torch")
 
 from mispmm import autograd, capi, capi_attn, ops  # noqa: E402
 
+import _attn_checks as checks  # noqa: E402
 import _attn_fused_ref as ref  # noqa: E402
+from _attn_checks import Case  # noqa: E402
 from _sddmm_bsr_ref import from_bits, full_mantissa, to_bits  # noqa: E402
 from _softmax_bsr_ref import pattern  # noqa: E402
-from test_gpu_softmax_bsr import _attention_tolerances, _dense_attention, bf, bits, dev, device_bsr, same_bits, trainable  # noqa: E402
+from test_gpu_softmax_bsr import bf, bits, dev, device_bsr, same_bits, trainable  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -34,15 +35,9 @@ def host(out):
     return from_bits(a) if a.dtype == np.int16 else a
 
 
-@functools.lru_cache(maxsize=None)
 def reference(name, d, dv, kind):
     """(float64 out, {out_bf16: tolerance}, exact lse, its tolerance) of head 0 of ref.operands(name, d, dv); read-only."""
-    q, k, v = (x[0] for x in ref.operands(name, d, dv))
-    mask, scale = ref.mask_of(name, kind), d ** -0.5
-    g = np.zeros((q.shape[0], dv), np.float32)
-    want = _dense_attention(pattern(name), q, k, v, g, scale, mask)[0]
-    tols = {ob: _attention_tolerances(name, q, k, v, g, scale, mask, ob)[0] for ob in (False, True)}
-    return (want, tols) + ref.lse_reference(name, q, k, mask, scale)
+    return checks.forward_reference(Case(name, d, dv, kind))
 
 
 def empty_rows(name):
@@ -58,23 +53,23 @@ def test_out_and_lse_against_float64_dense_masked_attention(name, d, dv, kind):
     q, k, v = (dbits(x[0]) for x in ref.operands(name, d, dv))
     mask = ref.mask_of(name, kind)
     md = None if mask is None else dev(mask)
-    want, tols, lse_exact, lse_tol = reference(name, d, dv, kind)
     empty = empty_rows(name)
     for out_bf16 in (False, True):
         out, lse = ops.attention_bsr_bf16(a, q, k, v, mask=md, out_bf16=out_bf16, return_lse=True)
         tag = capi_attn.last_kernel()
         assert tag == ref.tag_of(a.block_row_size, d, dv, mask is not None, out_bf16), tag
         assert out.shape == (a.num_rows, dv) and out.dtype == (torch.int16 if out_bf16 else torch.float32) and lse.shape == (a.num_rows,)
-        got, lse = host(out), lse.cpu().numpy()
-        err = np.abs(got.astype(np.float64) - want)
-        print(f"fused attention {name} D={d} Dv={dv} {kind} {tag} out: max |err| / tolerance = {float(np.max(err / tols[out_bf16])):.3g}")
-        assert np.all(err <= tols[out_bf16]), f"{name} D={d} Dv={dv} {kind} bf16={out_bf16}: out outside the composed tolerance"
+        # the checks of tests/_attn_checks.py: the functions tests/test_attn_mutants_cpu.py runs the faulty restatements through
+        case, got = Case(name, d, dv, kind, out_bf16=out_bf16), dict(out=host(out), lse=lse.cpu().numpy())
+        ok, worst = checks.out_composed(got, case)
+        print(f"fused attention {name} D={d} Dv={dv} {kind} {tag} out: max |err| / tolerance = {worst:.3g}")
+        assert ok, f"{name} D={d} Dv={dv} {kind} bf16={out_bf16}: out outside the composed tolerance"
         # an empty block row: +0 rows and lse = -Inf
-        assert empty.any() and not out.cpu().numpy().view(np.uint16 if out_bf16 else np.uint32)[empty].any()
-        assert np.array_equal(np.isneginf(lse), empty)
-        lerr = np.abs(lse[~empty].astype(np.float64) - lse_exact[~empty])
-        print(f"fused attention {name} D={d} Dv={dv} {kind} {tag} lse: max |err| / tolerance = {float(np.max(lerr / lse_tol[~empty])):.3g}")
-        assert np.all(lerr <= lse_tol[~empty]), f"{name} D={d} Dv={dv} {kind}: lse outside its bound"
+        assert empty.any() and not out.cpu().numpy().view(np.uint16 if out_bf16 else np.uint32)[empty].any() and checks.forward_zero_rows(got, case)[0]
+        assert np.array_equal(np.isneginf(got["lse"]), empty)
+        ok, worst = checks.lse_bound(got, case)
+        print(f"fused attention {name} D={d} Dv={dv} {kind} {tag} lse: max |err| / tolerance = {worst:.3g}")
+        assert ok, f"{name} D={d} Dv={dv} {kind}: lse outside its bound"
 
 
 @pytest.mark.parametrize("name", ["edges16", "edges32"])
@@ -88,9 +83,9 @@ def test_a_constant_v_comes_back_to_fp32_accuracy(name):
         for value in (1.0, -0.34765625):
             v = dbits(np.full((p.num_cols, dv), value, np.float32))
             out = ops.attention_bsr_bf16(a, q, k, v, mask=dev(ref.mask_of(name, "causal"))).cpu().numpy()
-            rel = np.abs(out[rows].astype(np.float64) / value - 1.0)
-            print(f"constant V {name} Dv={dv} value={value}: max rel / ((L + 16) u) = {float(np.max(rel / ((length[rows] + 16) * 2.0 ** -24)[:, None])):.3g}")
-            assert np.all(rel <= ((length[rows] + 16) * 2.0 ** -24)[:, None])
+            ok, worst = checks.constant_v(dict(out=out), Case(name, 64, dv, "causal", const_v=value))
+            print(f"constant V {name} Dv={dv} value={value}: max rel / ((L + 16) u) = {worst:.3g}")
+            assert ok and rows.any()
 
 
 @pytest.mark.parametrize("out_bf16", [False, True])

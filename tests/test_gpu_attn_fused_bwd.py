@@ -1,7 +1,9 @@
 """The fused block-sparse attention backward (mispmm_attn_bsr_bwd_bf16, ops.attention_bsr_bwd_bf16,
 block_sparse_attention(fused=True, fused_backward=True)) on the GPU.  References and tolerances: tests/_attn_fused_bwd_ref.py --
 dq, dk and dv against float64 dense masked attention (torch.autograd in float64) inside bwd_tolerances, the bound derived from
-the header's by first-order propagation; nothing is measured into it.
+the header's by first-order propagation; nothing is measured into it.  The numerical checks are the functions of
+tests/_attn_checks.py, which tests/test_attn_mutants_cpu.py runs deliberately faulty restatements through; the tighter, derived
+check on the kernel's own out and lse: tests/test_gpu_attn_tight.py.
 
 Worst |err| / tolerance printed on an MI355X (`-s` prints every one): fp32 gradients dq 0.227,
 dk 0.286, dv 0.783; bf16 gradients dq 0.299, dk 0.407, dv 0.781 (dv: the rounding of P to bf16, 2^-9 against the 2^-8 of the bound)."""
@@ -15,7 +17,9 @@ torch = pytest.importorskip("torch")
 
 from mispmm import autograd, capi_attn_bwd, ops  # noqa: E402
 
+import _attn_checks as checks  # noqa: E402
 import _attn_fused_bwd_ref as ref  # noqa: E402
+from _attn_checks import Case  # noqa: E402
 from _sddmm_bsr_ref import from_bits, to_bits  # noqa: E402
 from test_gpu_softmax_bsr import _attention_tolerances, _dense_attention, bf, bits, dev, same_bits  # noqa: E402
 
@@ -51,11 +55,9 @@ def dmask(name, kind):
     return None if m is None else dev(m)
 
 
-@functools.lru_cache(maxsize=None)
 def exact(name, d, dv, kind):
     """float64 (dq, dk, dv) of head 0 of ref.operands(name, d, dv); read-only."""
-    q, k, v, g = (x[0] for x in ref.operands(name, d, dv))
-    return _dense_attention(ref.bwd_pattern(name)[0], q, k, v, g, d ** -0.5, ref.mask_of(name, kind))[1:]
+    return checks.backward_exact(Case(name, d, dv, kind, src="bwd"))
 
 
 def forward(name, q, k, v, mask, out_bf16, scale=None):
@@ -84,20 +86,20 @@ def test_gradients_against_float64_dense_masked_attention(name, d, dv, kind):
     qh, kh, vh, gh = (x[0] for x in ref.operands(name, d, dv))
     q, k, v, g = (dbits(x) for x in (qh, kh, vh, gh))
     mask = dmask(name, kind)
-    want = exact(name, d, dv, kind)
     for out_bf16 in (False, True):
         out, lse = forward(name, q, k, v, mask, out_bf16)
         for grads_bf16 in (False, True):
             got = backward(name, q, k, v, out, lse, g, mask, grads_bf16=grads_bf16)
             tag = capi_attn_bwd.last_kernel()
             assert tag == ref.tag_of(bsr.block_row_size, d, dv, mask is not None), tag
-            tols = ref.bwd_tolerances(name, qh, kh, vh, gh, d ** -0.5, ref.mask_of(name, kind), out_bf16, grads_bf16)
-            for what, x, w, tol, rows in zip(("dq", "dk", "dv"), got, want, tols, (bsr.num_rows, bsr.num_cols, bsr.num_cols)):
+            for what, x, rows in zip(("dq", "dk", "dv"), got, (bsr.num_rows, bsr.num_cols, bsr.num_cols)):
                 assert x.dtype == (torch.int16 if grads_bf16 else torch.float32) and x.shape == (rows, dv if what == "dv" else d)
-                err = np.abs(host(x).astype(np.float64) - w)
-                print(f"fused backward {name} D={d} Dv={dv} {kind} out_bf16={out_bf16} grads_bf16={grads_bf16} {what}: "
-                      f"max |err| / tolerance = {float(np.max(err / tol)):.3g}")
-                assert np.all(err <= tol), f"{name} D={d} Dv={dv} {kind} out_bf16={out_bf16} grads_bf16={grads_bf16}: {what} outside the derived tolerance"
+            # the check of tests/_attn_checks.py: the function tests/test_attn_mutants_cpu.py runs the faulty restatements through
+            case = Case(name, d, dv, kind, src="bwd", out_bf16=out_bf16, grads_bf16=grads_bf16)
+            ok, worst = checks.bwd_composed(dict(dq=host(got[0]), dk=host(got[1]), dv=host(got[2])), case)
+            for what, w in zip(("dq", "dk", "dv"), worst):
+                print(f"fused backward {name} D={d} Dv={dv} {kind} out_bf16={out_bf16} grads_bf16={grads_bf16} {what}: max |err| / tolerance = {w:.3g}")
+            assert ok, f"{name} D={d} Dv={dv} {kind} out_bf16={out_bf16} grads_bf16={grads_bf16}: a gradient outside the derived tolerance {worst}"
 
 
 @pytest.mark.parametrize("grads_bf16", [False, True])
@@ -114,18 +116,9 @@ def test_empty_block_rows_and_columns_and_masked_columns_give_plus_zero_bits(nam
     if name.startswith("edgesT"):
         assert empty_cols[0] and empty_cols[-1]
     assert no_bits(dk, empty_cols) and no_bits(dv, empty_cols)
+    assert checks.backward_zero_rows(dict(dq=host(dq), dk=host(dk), dv=host(dv)), Case(name, 40, 72, "none", src="bwd", grads_bf16=grads_bf16))[0]
     # -Inf over every block of some block columns (every second non-empty one; every matrix row keeps a finite key or was empty)
-    counts = np.diff(np.asarray(tbsr.block_row_ptrs, dtype=np.int64))
-    cols_of = np.asarray(bsr.block_col_idxs, dtype=np.int64)
-    ptrs = np.asarray(bsr.block_row_ptrs, dtype=np.int64)
-    blank = np.zeros(counts.shape[0], bool)
-    blank[np.argwhere(counts > 0).ravel()[::2]] = True
-    for lo, hi in zip(ptrs[:-1], ptrs[1:]):                        # a block row must keep one block: unblank its last column if need be
-        if hi > lo and blank[cols_of[lo:hi]].all():
-            blank[cols_of[hi - 1]] = False
-    assert blank.any()
-    m = np.zeros((bsr.num_blocks, bs, bs), np.float32)
-    m[blank[cols_of]] = -np.inf
+    m, blank = checks.blank_columns_mask(bsr, tbsr)
     md = dev(m)
     out, lse = forward(name, q, k, v, md, False)
     assert bool(torch.isfinite(lse[torch.from_numpy(~empty_rows).cuda()]).all())
@@ -134,6 +127,7 @@ def test_empty_block_rows_and_columns_and_masked_columns_give_plus_zero_bits(nam
     assert no_bits(dk, masked | empty_cols) and no_bits(dv, masked | empty_cols)
     for t in (dq, dk, dv):
         assert not np.isnan(host(t)).any()
+    assert checks.backward_zero_rows(dict(dq=host(dq), dk=host(dk), dv=host(dv)), Case(name, 40, 72, "blankcols", src="bwd", grads_bf16=grads_bf16))[0]
 
 
 @pytest.mark.parametrize("name", ["ragged16", "edgesT32"])
@@ -189,6 +183,7 @@ def test_every_subset_of_need_has_the_bits_of_the_call_for_all_three(name, kind)
     bs = ref.bwd_pattern(name)[0].block_row_size
     out, lse = forward(name, q, k, v, mask, True)
     full = backward(name, q, k, v, out, lse, g, mask)
+    subsets = {}
     for need in itertools.product((False, True), repeat=3):
         got = backward(name, q, k, v, out, lse, g, mask, need=need)
         if any(need):
@@ -198,6 +193,8 @@ def test_every_subset_of_need_has_the_bits_of_the_call_for_all_three(name, kind)
                 same_bits(x, w, f"{name} {what} with need={need}")
             else:
                 assert x is None
+        subsets[need] = tuple(None if x is None else host(x) for x in got)
+    assert checks.subsets_equal(dict(dq=host(full[0]), dk=host(full[1]), dv=host(full[2]), subsets=subsets), Case(name, 64, 64, kind, src="bwd", out_bf16=True, grads_bf16=True))[0]
     # dv alone needs neither delta nor out's row pass: perm is not needed without a mask either
     if mask is None:
         a, at, _ = device(name)
