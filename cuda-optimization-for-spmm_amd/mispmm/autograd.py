@@ -30,8 +30,10 @@ Both gradients come back in bfloat16.  The CSR product with fp32 values and the 
     c = spmm_bf16(a, w, b)                             # forward: ops.spmm_csr_bf16, b bfloat16, c bfloat16 or float32
     c.sum().backward()                                 # b.grad (bfloat16): the same kernel on A^T; w.grad: ops.sddmm_csr, widened
 
-Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, a fused
-SDDMM + softmax, the column-compacted block layouts (their tiles are built on the host from the values), a device kernel for
+    out = sparse_attention(a, q, k, v, fused=True)     # float32: one launch for all heads (ops.attention_csr), [H, ...] operands
+
+Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, a fused backward and bf16 operands for the fused
+CSR attention, the column-compacted block layouts (their tiles are built on the host from the values), a device kernel for
 the blocks[perm] transpose."""
 import dataclasses
 from dataclasses import dataclass
@@ -166,7 +168,75 @@ def edge_softmax(a, scores, acc="reference"):
     return _EdgeSoftmax.apply(scores, a, acc)
 
 
-def sparse_attention(a, q, k, v, scale=None, acc="reference"):
+class _FusedSparseAttention(torch.autograd.Function):
+    """The forward in one launch for all heads (ops.attention_csr).  q, k, v are saved and the weights are not: the backward
+    recomputes the scores and P head by head with the FAST kernels of the four-launch forward and runs its gradient chain, so
+    the gradients are those of the unfused acc="fast" call, head by head, bit for bit."""
+    @staticmethod
+    def forward(ctx, q, k, v, a, scale, bias):
+        q, k, v = q.detach(), k.detach(), v.detach()
+        ctx.a, ctx.scale, ctx.bias = a, scale, bias
+        ctx.save_for_backward(q, k, v)
+        return ops.attention_csr(a.fwd, q, k, v, scale=scale, bias=bias)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        a, needs, scale, bias = ctx.a, ctx.needs_input_grad, ctx.scale, ctx.bias
+        if not any(needs[:3]):
+            return (None,) * 6
+        q, k, v = ctx.saved_tensors
+        heads = [None] if q.dim() == 2 else range(q.shape[0])
+        grads = ([], [], [])
+        for h in heads:
+            qh, kh, vh, gh = (t if h is None else t[h] for t in (q, k, v, grad_out))
+            bh = bias if bias is None or bias.dim() == 1 else bias[h]
+            if gh.stride(1) != 1 or gh.stride(0) < gh.shape[1]:      # e.g. out.sum().backward() hands in an expanded scalar
+                gh = gh.contiguous()
+            qs = qh * scale
+            s = ops.sddmm_csr(a.fwd, qs, kh, acc="fast")
+            p = ops.softmax_csr(a.fwd, s if bh is None else s + bh, acc="fast")
+            grad_q = grad_k = grad_v = None
+            if needs[2]:
+                grad_v = ops.spmm_csr(dataclasses.replace(a.tpattern, data=p[a.perm]), gh, acc="fast")
+            if needs[0] or needs[1]:
+                dp = ops.sddmm_csr(a.fwd, gh, vh, acc="fast")
+                ds = ops.softmax_csr_bwd(a.fwd, p, dp, acc="fast")
+                if needs[0]:
+                    grad_q = ops.spmm_csr(dataclasses.replace(a.fwd, data=ds), kh, acc="fast") * scale
+                if needs[1]:
+                    grad_k = ops.spmm_csr(dataclasses.replace(a.tpattern, data=ds[a.perm]), qs, acc="fast")
+            for held, grad in zip(grads, (grad_q, grad_k, grad_v)):
+                held.append(grad)
+        merged = [None if held[0] is None else (held[0] if q.dim() == 2 else torch.stack(held)) for held in grads]
+        return (*merged, None, None, None)
+
+
+def _fused_sparse_attention(a, q, k, v, scale, bias):
+    dtype = a.fwd.data.dtype
+    if dtype != torch.float32:
+        raise ValueError("fused=True takes a float32 matrix: the fused kernel has one arithmetic, fp32")
+    dims = {t.dim() for t in (q, k, v)}
+    if dims not in ({2}, {3}):
+        raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    for t, rows, what in ((q, a.fwd.num_rows, "q"), (k, a.fwd.num_cols, "k"), (v, a.fwd.num_cols, "v")):
+        if t.dtype != dtype:
+            raise ValueError(f"{what} must be {dtype}, like the matrix")
+        if t.shape[-2] != rows or t.shape[:-2] != q.shape[:-2]:
+            raise ValueError(f"{what} must be [{rows}, N] or [H, {rows}, N] with q's H, not {tuple(t.shape)}")
+        if t.shape[-1] > 1 and t.stride(-1) != 1:
+            raise ValueError(f"{what} must have unit column stride")
+    if q.shape[-1] != k.shape[-1]:
+        raise ValueError(f"q and k must have the same number of columns, not {q.shape[-1]} and {k.shape[-1]}")
+    heads = q.shape[0] if q.dim() == 3 else 1
+    if bias is not None and tuple(bias.shape) not in ((a.fwd.nnz,), (heads, a.fwd.nnz)):
+        raise ValueError(f"bias must be [{a.fwd.nnz}] or [{heads}, {a.fwd.nnz}], not {tuple(bias.shape)}")
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    return _FusedSparseAttention.apply(q, k, v, a, float(scale), bias)
+
+
+def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=False):
     """Attention on A's pattern: row r attends to the columns A stores in row r.
 
         scores = sddmm(a, q * scale, k)        # [nnz]   <q_r, k_c> for every stored (r, c)
@@ -175,8 +245,25 @@ def sparse_attention(a, q, k, v, scale=None, acc="reference"):
 
     a: TrainableCSR [M x K] (its values are not read); q: [M, D], k: [K, D], v: [K, Dv] device tensors of a's dtype (float32
     or float64), unit column stride.  scale defaults to D ** -0.5 and is applied to q by a torch multiply.  Differentiable in
-    q, k and v; a row of A without entries gives a zero row."""
-    ops._require_gpu(a.fwd.row_ptrs, q, k, v)
+    q, k and v; a row of A without entries gives a zero row.
+    bias: a tensor of a's dtype over A's entries ([nnz]), added to the scores by a torch add before the softmax; -Inf = a
+    masked entry.  It is a constant: one that requires a gradient is refused.
+    fused=True (float32 only; off by default): the forward is ONE launch for all heads (ops.attention_csr: online softmax in
+    fp32, the scale applied to the scores by the kernel's fma, neither scores nor P written); q, k, v may then be [H, M, D] /
+    [H, K, D] / [H, K, Dv] with any head and row strides and out is [H, M, Dv]; bias [nnz] or [H, nnz]; acc is not read: the
+    kernel has one arithmetic, the FAST one.  out differs from the unfused result by roundings and is held to the same
+    tolerance.  q, k, v are saved and P is not: the backward recomputes the scores and P per head with the FAST kernels
+    (ops.sddmm_csr on q * scale, a torch add of the bias, ops.softmax_csr) and runs the chain above, so the gradients are the
+    unfused acc="fast" path's, head by head, bit for bit.  Without bias and fused the call is what it always was."""
+    ops._require_gpu(a.fwd.row_ptrs, q, k, v, bias)
+    if bias is not None:
+        if bias.requires_grad:
+            raise ValueError("bias is a constant: it gets no gradient and must not require one")
+        if bias.dtype != a.fwd.data.dtype:
+            raise ValueError(f"bias must be {a.fwd.data.dtype}, like the matrix")
+        bias = bias.detach()
+    if fused:
+        return _fused_sparse_attention(a, q, k, v, scale, bias)
     dtype = a.fwd.data.dtype
     _check_operand(q, a.fwd.num_rows, dtype, "q")
     _check_operand(k, a.fwd.num_cols, dtype, "k")
@@ -185,7 +272,11 @@ def sparse_attention(a, q, k, v, scale=None, acc="reference"):
         raise ValueError(f"q and k must have the same number of columns, not {q.shape[1]} and {k.shape[1]}")
     if scale is None:
         scale = q.shape[1] ** -0.5
-    return spmm(a, edge_softmax(a, sddmm(a, q * scale, k, acc=acc), acc=acc), v, acc=acc)
+    if bias is None:
+        return spmm(a, edge_softmax(a, sddmm(a, q * scale, k, acc=acc), acc=acc), v, acc=acc)
+    if bias.dim() != 1 or bias.shape[0] != a.fwd.nnz:
+        raise ValueError(f"bias must hold the {a.fwd.nnz} entries of A, not {tuple(bias.shape)}")
+    return spmm(a, edge_softmax(a, sddmm(a, q * scale, k, acc=acc) + bias, acc=acc), v, acc=acc)
 
 
 @dataclass

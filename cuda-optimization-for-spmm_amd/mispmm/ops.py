@@ -603,6 +603,86 @@ def softmax_csr_bwd(a, p, dp, out=None, acc="reference", stream=None):
     return out
 
 
+ATTN_CSR_MAX_WIDTH = 256     # D and Dv of the fused CSR attention kernel: 1 up to this (mispmm_attn_csr.h)
+
+
+def _attn_csr_operand(t, rows, heads, what):
+    """(t as [H, rows, width], row stride, head stride) of a float32 operand given as [rows, width] or [H, rows, width]."""
+    if t.dtype != torch.float32 or t.dim() not in (2, 3):
+        raise ValueError(f"{what} must be a float32 tensor, [{rows}, width] or [H, {rows}, width], not {t.dtype} {tuple(t.shape)}")
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.shape[1] != rows or (heads is not None and t.shape[0] != heads):
+        raise ValueError(f"{what} must be [{rows}, width] or [{'H' if heads is None else heads}, {rows}, width], not {tuple(t.shape)}")
+    width = t.shape[2]
+    if width > 1 and t.stride(2) != 1:
+        raise ValueError(f"{what} must have unit column stride")
+    if width == 0 or width > ATTN_CSR_MAX_WIDTH:
+        raise ValueError(f"the fused CSR attention kernel takes widths from 1 to {ATTN_CSR_MAX_WIDTH}: {what} has {width} columns")
+    ld = t.stride(1) if rows > 1 else max(width, t.stride(1))
+    if ld < width or any(s < 0 for s in t.stride()):
+        raise ValueError(f"{what} must not overlap its own rows (row stride {ld} < {width} columns), e.g. an expanded tensor")
+    return t, ld, (t.stride(0) if t.shape[0] > 1 else 0)
+
+
+def attention_csr(a, q, k, v, scale=None, bias=None, return_lse=False, out=None, lse=None, stream=None):
+    """Fused attention on a CSR pattern (mispmm_attn_csr_f32, libmispmm_attn_csr.so): for every head, out = softmax over each
+    row's stored entries of (scale * <q_r, k_c> + bias), times v -- one launch for all heads, neither the scores nor the
+    weights written.  a: a float32 DeviceCSR [M x K] (index arrays used, values unread); q: [M, D], k: [K, D], v: [K, Dv]
+    float32, or [H, ...] with any head and row strides and unit column stride (a permuted [M, H, D]; k, v expanded over the
+    heads for multi-query attention); D and Dv from 1 to 256.  scale defaults to D ** -0.5.  bias: float32 [nnz], shared by
+    the heads, or [H, nnz], in A's entry order, added to the scaled scores, -Inf = masked.  Returns out, [M, Dv] or
+    [H, M, Dv]; with return_lse (out, lse), lse the [M] or [H, M] log-sum-exp of each row.  out= and lse= take the results
+    where given: out of the result's shape with unit column stride, lse contiguous."""
+    from . import capi_attn_csr
+    _require_gpu(a.row_ptrs, q, k, v, bias, out, lse)
+    if a.data.dtype != torch.float32:
+        raise ValueError("attention_csr takes a float32 DeviceCSR")
+    if q.dim() != k.dim() or q.dim() != v.dim():
+        raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    batched = q.dim() == 3
+    q3, ldq, q_head = _attn_csr_operand(q, a.num_rows, None, "q")
+    heads = q3.shape[0]
+    k3, ldk, k_head = _attn_csr_operand(k, a.num_cols, heads, "k")
+    v3, ldv, v_head = _attn_csr_operand(v, a.num_cols, heads, "v")
+    d, dv = q3.shape[2], v3.shape[2]
+    if k3.shape[2] != d:
+        raise ValueError(f"q and k must have the same number of columns, not {d} and {k3.shape[2]}")
+    bias_head = 0
+    if bias is not None:
+        if bias.dtype != torch.float32 or tuple(bias.shape) not in ((a.nnz,), (heads, a.nnz)) or (a.nnz > 1 and bias.stride(-1) != 1):
+            raise ValueError(f"bias must be a float32 tensor of shape ({a.nnz},) or ({heads}, {a.nnz}) with unit stride along the entries, "
+                             f"not {bias.dtype} {tuple(bias.shape)}")
+        if bias.dim() == 2 and heads > 1:
+            bias_head = bias.stride(0)
+            if bias_head < 0:
+                raise ValueError("bias must not have a negative head stride")
+    if scale is None:
+        scale = d ** -0.5
+    shape = (heads, a.num_rows, dv)
+    if out is None:
+        out3 = torch.empty(shape, dtype=torch.float32, device=q.device)
+    else:
+        if out.dtype != torch.float32 or out.dim() != q.dim():
+            raise ValueError(f"out must be a float32 tensor of shape {shape if batched else shape[1:]} with unit column stride")
+        out3 = out if batched else out.unsqueeze(0)
+        if tuple(out3.shape) != shape or (dv > 1 and out3.stride(2) != 1) or (shape[1] > 1 and out3.stride(1) < dv) \
+                or (heads > 1 and out3.stride(0) < 1):
+            raise ValueError(f"out must be a float32 tensor of shape {shape if batched else shape[1:]} with unit column stride")
+    lse_shape = (heads, a.num_rows) if batched else (a.num_rows,)
+    if lse is None and return_lse:
+        lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
+    if lse is not None and (lse.dtype != torch.float32 or tuple(lse.shape) != lse_shape or not lse.is_contiguous()):
+        raise ValueError(f"lse must be a contiguous float32 tensor of shape {lse_shape}")
+    ldo = out3.stride(1) if shape[1] > 1 else max(dv, out3.stride(1))
+    o_head = out3.stride(0) if heads > 1 else 0
+    capi_attn_csr.check(capi_attn_csr.lib().mispmm_attn_csr_f32(
+        _stream_ptr(stream), heads, a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs), _p(q3), q_head, ldq, _p(k3), k_head, ldk, d,
+        _p(v3), v_head, ldv, dv, float(scale), _p(bias), bias_head, _p(out3), o_head, ldo, _p(lse)))
+    result = out if out is not None else (out3 if batched else out3[0])
+    return (result, lse) if return_lse else result
+
+
 @dataclass
 class DeviceCSRTiles:
     """A CSR with rows of one width grouped into LDS tiles (mispmm_csr_tiles_host): rows that share B rows sit in one tile of

@@ -585,8 +585,9 @@ int mispmm_csr_transpose_host(uint32_t M, uint32_t K, uint32_t nnz, const uint32
  * pointer is MISPMM_ERR_INVALID_ARG, found before any device work; nnz == 0 or M == 0 is a no-op.  The kernels address
  * through 64-bit pointers: no array size is declined.  Enqueues only: one launch, no allocation, no synchronisation,
  * capturable.  mispmm_last_kernel() = softmax_csr<...> / softmax_csr_bwd<...> (arithmetic, G lanes per row, R entries per
- * lane held in registers).  Not built: a split form that deals one very long row to several waves, a fused
- * SDDMM + softmax, bf16, COO / ELL patterns. */
+ * lane held in registers).  Not built: a split form that deals one very long row to several waves, bf16, COO / ELL
+ * patterns.  The fused form -- scores, softmax and the product with V in one launch for all heads, fp32 -- is a library
+ * of its own beside this one, with a header of its own (fused attention on a CSR pattern). */
 int mispmm_softmax_csr_f32(mispmm_stream_t stream, uint32_t M, uint32_t nnz, const uint32_t *rowPtrs, const float *scores,
                            float *out, int acc_mode);
 int mispmm_softmax_csr_f64(mispmm_stream_t stream, uint32_t M, uint32_t nnz, const uint32_t *rowPtrs, const double *scores,
