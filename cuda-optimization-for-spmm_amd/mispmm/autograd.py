@@ -31,9 +31,10 @@ Both gradients come back in bfloat16.  The CSR product with fp32 values and the 
     c.sum().backward()                                 # b.grad (bfloat16): the same kernel on A^T; w.grad: ops.sddmm_csr, widened
 
     out = sparse_attention(a, q, k, v, fused=True)     # float32: one launch for all heads (ops.attention_csr), [H, ...] operands
+    out = sparse_attention(a, q, k, v, fused=True, fused_backward=True)   # ... and the backward in at most two (ops.attention_csr_bwd)
 
-Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, a fused backward and bf16 operands for the fused
-CSR attention, the column-compacted block layouts (their tiles are built on the host from the values), a device kernel for
+Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, bf16 operands for the fused CSR attention and a
+gradient for its bias, the column-compacted block layouts (their tiles are built on the host from the values), a device kernel for
 the blocks[perm] transpose."""
 import dataclasses
 from dataclasses import dataclass
@@ -51,6 +52,14 @@ class TrainableCSR:
     tpattern: ops.DeviceCSR     # A^T's pattern
     perm: torch.Tensor          # int64, device: entry t of A^T is entry perm[t] of A
     values: torch.Tensor        # a device copy of csr.data for the caller to wrap as a parameter
+
+    _perm32: tuple = dataclasses.field(default=None, repr=False, compare=False)   # (perm it was made from, its int32 copy)
+
+    def perm32(self):
+        """perm as the 32-bit array the fused attention backward reads: converted once per perm tensor, then kept."""
+        if self._perm32 is None or self._perm32[0] is not self.perm:
+            self._perm32 = (self.perm, self.perm.to(torch.int32).contiguous())
+        return self._perm32[1]
 
     @staticmethod
     def from_host(csr, device="cuda", dtype=torch.float32):
@@ -212,7 +221,32 @@ class _FusedSparseAttention(torch.autograd.Function):
         return (*merged, None, None, None)
 
 
-def _fused_sparse_attention(a, q, k, v, scale, bias):
+class _FusedSparseAttentionFusedBwd(torch.autograd.Function):
+    """Forward and backward fused (ops.attention_csr with its lse, ops.attention_csr_bwd): q, k, v, out and lse are saved, and
+    the backward is ONE call, at most two launches for all heads, with `need` set from the inputs that require a gradient."""
+    @staticmethod
+    def forward(ctx, q, k, v, a, scale, bias):
+        q, k, v = q.detach(), k.detach(), v.detach()
+        out, lse = ops.attention_csr(a.fwd, q, k, v, scale=scale, bias=bias, return_lse=True)
+        ctx.a, ctx.scale, ctx.bias = a, scale, bias
+        ctx.save_for_backward(q, k, v, out, lse)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        a, needs = ctx.a, ctx.needs_input_grad
+        if not any(needs[:3]):
+            return (None,) * 6
+        q, k, v, out, lse = ctx.saved_tensors
+        if grad_out.stride(-1) != 1 or grad_out.stride(-2) < grad_out.shape[-1] or (grad_out.dim() == 3 and grad_out.stride(0) < 1):
+            grad_out = grad_out.contiguous()                       # e.g. out.sum().backward() hands in an expanded scalar
+        grads = ops.attention_csr_bwd(a.fwd, a.tpattern, a.perm32(), q, k, v, out, lse, grad_out, scale=ctx.scale, bias=ctx.bias,
+                                      need=tuple(needs[:3]))
+        return (*grads, None, None, None)
+
+
+def _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward=False):
     dtype = a.fwd.data.dtype
     if dtype != torch.float32:
         raise ValueError("fused=True takes a float32 matrix: the fused kernel has one arithmetic, fp32")
@@ -233,10 +267,12 @@ def _fused_sparse_attention(a, q, k, v, scale, bias):
         raise ValueError(f"bias must be [{a.fwd.nnz}] or [{heads}, {a.fwd.nnz}], not {tuple(bias.shape)}")
     if scale is None:
         scale = q.shape[-1] ** -0.5
+    if fused_backward:
+        return _FusedSparseAttentionFusedBwd.apply(q, k, v, a, float(scale), bias)
     return _FusedSparseAttention.apply(q, k, v, a, float(scale), bias)
 
 
-def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=False):
+def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=False, fused_backward=False):
     """Attention on A's pattern: row r attends to the columns A stores in row r.
 
         scores = sddmm(a, q * scale, k)        # [nnz]   <q_r, k_c> for every stored (r, c)
@@ -254,7 +290,14 @@ def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=F
     kernel has one arithmetic, the FAST one.  out differs from the unfused result by roundings and is held to the same
     tolerance.  q, k, v are saved and P is not: the backward recomputes the scores and P per head with the FAST kernels
     (ops.sddmm_csr on q * scale, a torch add of the bias, ops.softmax_csr) and runs the chain above, so the gradients are the
-    unfused acc="fast" path's, head by head, bit for bit.  Without bias and fused the call is what it always was."""
+    unfused acc="fast" path's, head by head, bit for bit.  Without bias and fused the call is what it always was.
+    fused_backward=True (needs fused=True; off by default): the forward also returns its log-sum-exp and q, k, v, out and lse
+    are saved; the backward is ONE ops.attention_csr_bwd call, at most two launches for all heads (a row pass for dq, a column
+    pass on A^T's pattern for dk and dv), nothing recomputed through memory, work for inputs that need no gradient skipped.
+    Its gradients are not the chain's bits -- P comes from the stored lse and the softmax backward's row term from
+    <grad_out, out> -- and are held to derived tolerances (include/mispmm_attn_csr_bwd.h, NUMERICS)."""
+    if fused_backward and not fused:
+        raise ValueError("fused_backward=True needs fused=True: the fused backward reads the fused forward's out and lse")
     ops._require_gpu(a.fwd.row_ptrs, q, k, v, bias)
     if bias is not None:
         if bias.requires_grad:
@@ -263,7 +306,7 @@ def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=F
             raise ValueError(f"bias must be {a.fwd.data.dtype}, like the matrix")
         bias = bias.detach()
     if fused:
-        return _fused_sparse_attention(a, q, k, v, scale, bias)
+        return _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward)
     dtype = a.fwd.data.dtype
     _check_operand(q, a.fwd.num_rows, dtype, "q")
     _check_operand(k, a.fwd.num_cols, dtype, "k")

@@ -683,6 +683,92 @@ def attention_csr(a, q, k, v, scale=None, bias=None, return_lse=False, out=None,
     return (result, lse) if return_lse else result
 
 
+def _attn_csr_result(t, shape, batched, what):
+    """(t as [H, rows, width], row stride, head stride) of a float32 tensor the backward reads or writes."""
+    t3 = t if batched else t.unsqueeze(0)
+    if t.dtype != torch.float32 or t.dim() != (3 if batched else 2) or tuple(t3.shape) != shape or (shape[2] > 1 and t3.stride(2) != 1) \
+            or (shape[1] > 1 and t3.stride(1) < shape[2]) or any(s < 0 for s in t3.stride()):
+        raise ValueError(f"{what} must be a float32 tensor of shape {shape if batched else shape[1:]} with unit column stride and rows that "
+                         f"do not overlap, not {t.dtype} {tuple(t.shape)} with strides {tuple(t.stride())}")
+    return t3, (t3.stride(1) if shape[1] > 1 else max(shape[2], t3.stride(1))), (t3.stride(0) if shape[0] > 1 else 0)
+
+
+def attention_csr_bwd(a, at, perm, q, k, v, out, lse, grad_out, scale=None, bias=None, need=(True, True, True), dq=None, dk=None, dv=None,
+                      delta=None, stream=None):
+    """Fused backward of attention_csr (mispmm_attn_csr_bwd_f32, libmispmm_attn_csr_bwd.so): (dq, dk, dv) for every head in at
+    most two launches, the scores, the weights and their gradients never written.  a: the forward's DeviceCSR; at, perm: A^T's
+    pattern and the permutation of its entries (csr_transpose; TrainableCSR.tpattern / .perm32()), perm an integer device
+    tensor (int64 is converted to 32 bits here: hand in int32 to avoid the copy), read only with a bias.  q, k, v, scale, bias:
+    as in the forward; out, lse: what the forward returned; grad_out: float32 of out's shape.  2-D or [H, ...] operands with
+    any head and row strides and unit column stride.  need: which of (dq, dk, dv) to compute; the others come back None and
+    their work is skipped.  dk and dv are [H, K, ...] also where k and v are one head expanded over all.  dq= / dk= / dv= take
+    the gradients where given.  delta: a contiguous float32 workspace of lse's shape, allocated here unless given; needed
+    for dq and dk."""
+    from . import capi_attn_csr_bwd
+    _require_gpu(a.row_ptrs, at.row_ptrs, perm, q, k, v, out, lse, grad_out, bias, dq, dk, dv, delta)
+    if a.data.dtype != torch.float32:
+        raise ValueError("attention_csr_bwd takes a float32 DeviceCSR")
+    if (at.num_rows, at.num_cols, at.nnz) != (a.num_cols, a.num_rows, a.nnz):
+        raise ValueError(f"at must be the pattern of A^T: {a.num_cols} x {a.num_rows} with {a.nnz} entries")
+    if len({q.dim(), k.dim(), v.dim(), out.dim(), grad_out.dim()}) != 1:
+        raise ValueError("q, k, v, out and grad_out must all be 2-D or all [H, ...]")
+    batched = q.dim() == 3
+    q3, ldq, q_head = _attn_csr_operand(q, a.num_rows, None, "q")
+    heads = q3.shape[0]
+    k3, ldk, k_head = _attn_csr_operand(k, a.num_cols, heads, "k")
+    v3, ldv, v_head = _attn_csr_operand(v, a.num_cols, heads, "v")
+    d, dvw = q3.shape[2], v3.shape[2]
+    if k3.shape[2] != d:
+        raise ValueError(f"q and k must have the same number of columns, not {d} and {k3.shape[2]}")
+    o3, ldo, o_head = _attn_csr_result(out, (heads, a.num_rows, dvw), batched, "out")
+    g3, ldg, g_head = _attn_csr_result(grad_out, (heads, a.num_rows, dvw), batched, "grad_out")
+    rows_shape = (heads, a.num_rows) if batched else (a.num_rows,)
+    if lse.dtype != torch.float32 or tuple(lse.shape) != rows_shape or not lse.is_contiguous():
+        raise ValueError(f"lse must be a contiguous float32 tensor of shape {rows_shape}")
+    bias_head = 0
+    if bias is not None:
+        if bias.dtype != torch.float32 or tuple(bias.shape) not in ((a.nnz,), (heads, a.nnz)) or (a.nnz > 1 and bias.stride(-1) != 1):
+            raise ValueError(f"bias must be a float32 tensor of shape ({a.nnz},) or ({heads}, {a.nnz}) with unit stride along the entries, "
+                             f"not {bias.dtype} {tuple(bias.shape)}")
+        if bias.dim() == 2 and heads > 1:
+            bias_head = bias.stride(0)
+            if bias_head < 0:
+                raise ValueError("bias must not have a negative head stride")
+    if len(need) != 3:
+        raise ValueError("need holds three flags: (dq, dk, dv)")
+    if perm is not None:
+        if perm.dtype not in (torch.int32, torch.int64) or perm.numel() != a.nnz:
+            raise ValueError(f"perm must hold {a.nnz} int32 or int64 entry numbers")
+        if perm.dtype == torch.int64:
+            perm = perm.to(torch.int32)
+        perm = perm.contiguous()
+    elif bias is not None and (need[1] or need[2]):
+        raise ValueError("with a bias, dk and dv need perm")
+    if scale is None:
+        scale = d ** -0.5
+    grads = []
+    for wanted, given, rows, width, what in ((need[0], dq, a.num_rows, d, "dq"), (need[1], dk, a.num_cols, d, "dk"), (need[2], dv, a.num_cols, dvw, "dv")):
+        if not wanted:
+            grads.append((None, None, 0, 0))
+            continue
+        shape = (heads, rows, width)
+        if given is None:
+            given = torch.empty(shape if batched else shape[1:], dtype=torch.float32, device=q.device)
+        t3, ld, head = _attn_csr_result(given, shape, batched, what)
+        grads.append((given, t3, ld, head))
+    if need[0] or need[1]:
+        if delta is None:
+            delta = torch.empty(rows_shape, dtype=torch.float32, device=q.device)
+        elif delta.dtype != torch.float32 or tuple(delta.shape) != rows_shape or not delta.is_contiguous():
+            raise ValueError(f"delta must be a contiguous float32 tensor of shape {rows_shape}")
+    (rq, q_out, lddq, dq_head), (rk, k_out, lddk, dk_head), (rv, v_out, lddv, dv_head) = grads
+    capi_attn_csr_bwd.check(capi_attn_csr_bwd.lib().mispmm_attn_csr_bwd_f32(
+        _stream_ptr(stream), heads, a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs), _p(at.row_ptrs), _p(at.col_idxs), _p(perm),
+        _p(q3), q_head, ldq, _p(k3), k_head, ldk, d, _p(v3), v_head, ldv, dvw, float(scale), _p(bias), bias_head, _p(o3), o_head, ldo, _p(lse),
+        _p(g3), g_head, ldg, _p(delta), _p(q_out), dq_head, lddq, _p(k_out), dk_head, lddk, _p(v_out), dv_head, lddv))
+    return rq, rk, rv
+
+
 @dataclass
 class DeviceCSRTiles:
     """A CSR with rows of one width grouped into LDS tiles (mispmm_csr_tiles_host): rows that share B rows sit in one tile of
