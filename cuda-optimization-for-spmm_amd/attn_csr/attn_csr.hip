@@ -4,59 +4,30 @@
 //   z[e]      = fma(scale, <Q_h[r, :D], K_h[c, :D]>, bias_h[e])          c = colIdxs[e], e over the stored entries of row r
 //   out_h[r]  = sum_e softmax_e(z) * V_h[c, :Dv]
 //
-// Shape: the two halves are those of csrc/sddmm.hip and csrc/row_gather.hpp, in one lane group.  G lanes own one (head, row);
-// a lane owns VEC consecutive columns of each of NCH column chunks of G * VEC and holds its slice of Q[r] and of the fp32
-// accumulator O in registers (G and NCH from max(D, Dv): every width up to 256 is held, there is no re-reading form).  The
-// row's entries are walked in batches of 8.  A batch's 8 x NCH K-row reads and 8 x NCH V-row reads are issued together, the K
-// reads first: the vector-memory counter is in order, so the dot products wait for K alone and V arrives under them and under
-// the softmax arithmetic.  The column keys (and the bias) of a batch are fetched one batch ahead.  V is NOT fetched a batch
-// ahead: a second register stage of 8 x NCH vectors would double the kernel's largest array for a latency the K-side
-// arithmetic already covers.
-// Scores: every lane sums its columns' products for the 8 entries (one fma chain each), then the TRANSPOSING butterfly of
-// sddmm.hip leaves the score of entry i in lane i of every 8-lane segment of the group -- the further doublings of G add
-// commutatively, so all segments hold the same bits and the softmax arithmetic below runs redundantly in each of them with
-// no broadcast between segments.
+// Shape: the two halves are those of csrc/sddmm.hip and csrc/row_gather.hpp, in the lane group of lane_group.hpp (G lanes per
+// (head, row), batches of 8 entries, the transposing butterfly, the saturating join of dropped offsets: all explained there).
+// A lane holds its slice of Q[r] and of the fp32 accumulator O.  A batch's 8 x NCH K-row reads and 8 x NCH V-row reads are
+// issued together, the K reads first: the vector-memory counter is in order, so the dot products wait for K alone and V
+// arrives under them and under the softmax arithmetic.  The column keys (and the bias) of a batch are fetched one batch ahead.
+// V is NOT fetched a batch ahead: a second register stage of 8 x NCH vectors would double the kernel's largest array for a
+// latency the K-side arithmetic already covers.
 // Online softmax per batch: the batch maximum over the 8 lanes of a segment (3 moves), folded into the running maximum m;
 // mu = m with an infinite m replaced by 0 (what torch.logsumexp subtracts); alpha = exp(mu_old - mu_new), exactly 1 while m
 // is still -Inf; one v_exp_f32 per lane for the weight; the 8 weights are summed by a fixed tree over the segment (3 moves)
 // into l = fl(fl(l * alpha) + t) and reach the group by DPP row_newbcast for O = fl(alpha * O), then O = fma(w_i, V[c_i], O)
 // for i = 0..7.  Every lane of the group holds the same alpha bits, so O and l are scaled by the same number.
 // After the row: out = O / l (an IEEE division per element), lse = mu + log l.
-// Dead slots of a last batch and lanes past D or Dv read through the dropped-load offset, and the key and the lane offset
-// are joined by a SATURATING add: two dropped halves stay dropped instead of wrapping to offset 0, so row 0 of K or V is
-// never read on their behalf.  A dead slot's score is replaced by -Inf before the maximum: its weight is exp2(-Inf) = +0.
+// A dead slot's score is replaced by -Inf before the maximum: its weight is exp2(-Inf) = +0.
 // The bias is read through a descriptor of its own that spans nothing where there is no bias: every read then returns +0
-// and no branch stands in the loop.  Heads are the slow axis of the flattened grid and the (head, row block) items go over
-// the XCDs by xcd_grid, so an XCD walks one head's rows at a time.  No LDS, no atomics, no scratch; fixed order throughout:
-// run to run identical.
+// and no branch stands in the loop.  Run to run identical.
 // The sources lie outside csrc/, fused/ and rows_bf16/: the census tests hold those directories and their libraries to their
 // records.
-#include "lane_moves.hpp"
+#include "lane_group.hpp"
 #include "mispmm_attn_csr.h"
 
 namespace mispmm {
 
 namespace {
-
-constexpr int kAcBlock = 256;  // threads per workgroup
-constexpr int kAcBatch = 8;    // entries of a row per step: lane i of an 8-lane segment holds the i-th score
-constexpr int kAcMaxWidth = 256;
-
-__device__ __forceinline__ float ac_exp(float t) { return __builtin_amdgcn_exp2f(t * 1.44269504088896340736f); }  // as softmax_csr.hip, FAST
-
-// key + lane offset where either may be the dropped-load mark: saturating, so that two marks do not wrap to offset 0
-__device__ __forceinline__ uint32_t join_off(uint32_t key, uint32_t off) { return __builtin_elementwise_add_sat(key, off); }
-
-// one step of the transposing butterfly (sddmm.hip): 2 * H values in, H out; the lane whose bit MASK is clear keeps the even ones
-template <int MASK, int H>
-__device__ __forceinline__ void fold(const float *in, float *out, bool odd) {
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        const float keep = odd ? in[2 * j + 1] : in[2 * j];
-        const float send = odd ? in[2 * j] : in[2 * j + 1];
-        out[j] = keep + lane_xor<MASK>(send);
-    }
-}
 
 struct AcParams {
     uint32_t M, D, Dv, blocks_per_head, total, xcd_chunk;
@@ -67,15 +38,15 @@ struct AcParams {
 };
 
 template <int G, int VEC, int NCH>
-__global__ void __launch_bounds__(kAcBlock) attn_csr_kernel(const AcParams p, const uint32_t *__restrict__ rowPtrs,
+__global__ void __launch_bounds__(kLgBlock) attn_csr_kernel(const AcParams p, const uint32_t *__restrict__ rowPtrs,
                                                             const uint32_t *__restrict__ colIdxs, const float *__restrict__ Q,
                                                             const float *__restrict__ K, const float *__restrict__ V,
                                                             const float *__restrict__ bias, float *__restrict__ out,
                                                             float *__restrict__ lse_out) {
     using vec_t = typename VecOf<VEC>::type;
-    static_assert(G >= kAcBatch && (G & (G - 1)) == 0 && G <= kWave, "a batch's scores sit in the first lanes of a group");
+    static_assert(G >= kLgBatch && (G & (G - 1)) == 0 && G <= kWave, "a batch's scores sit in the first lanes of a group");
     static_assert(NCH == 1 || G == kWave, "more than one chunk only where a whole wave owns the row");
-    constexpr int GROUPS = kAcBlock / G, E = kAcBatch;
+    constexpr int GROUPS = kLgBlock / G, E = kLgBatch;
     constexpr uint32_t CHUNK = G * VEC;
     const uint32_t lane = threadIdx.x % G, sub = lane & (E - 1);
     const uint32_t item = xcd_block(blockIdx.x, p.xcd_chunk);
@@ -119,9 +90,8 @@ __global__ void __launch_bounds__(kAcBlock) attn_csr_kernel(const AcParams p, co
     vec_t xv[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-        const uint32_t col = c * CHUNK + lane * VEC;
-        koff[c] = col < p.D ? col * 4u : kDropLoad;
-        voff[c] = col < p.Dv ? col * 4u : kDropLoad;
+        koff[c] = lane_off<G, VEC>(lane, c, p.D);
+        voff[c] = lane_off<G, VEC>(lane, c, p.Dv);
         xv[c] = buffer_load_vec<VEC>(qr, join_off(row * p.ldq * 4u, koff[c]), 0);  // past D: zeros
     }
     // entry c0 + sub of the row and its bias: every 8-lane segment of the group holds the batch's 8 entries.  A slot past the
@@ -147,18 +117,8 @@ __global__ void __launch_bounds__(kAcBlock) attn_csr_kernel(const AcParams p, co
         fetch(s0 + E, nxt_col, nxt_bias);  // on its way while this batch is gathered
         __builtin_amdgcn_sched_barrier(0);  // ... issued here, ahead of the batch's own reads (see the end of the loop body)
         vec_t kv[E][NCH], vv[E][NCH];
-        static_for<0, E>([&](auto j_tag) {
-            constexpr int j = decltype(j_tag)::value;
-            const uint32_t kj = group_bcast<8, j>(kkey);
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) kv[j][c] = buffer_load_vec<VEC>(kr, join_off(kj, koff[c]), 0);
-        });
-        static_for<0, E>([&](auto j_tag) {
-            constexpr int j = decltype(j_tag)::value;
-            const uint32_t vj = group_bcast<8, j>(vkey);
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) vv[j][c] = buffer_load_vec<VEC>(vr, join_off(vj, voff[c]), 0);
-        });
+        gather_rows<VEC, NCH>(kkey, kr, koff, kv);
+        gather_rows<VEC, NCH>(vkey, vr, voff, vv);
         float acc[E];
 #pragma unroll
         for (int j = 0; j < E; ++j) {
@@ -166,16 +126,9 @@ __global__ void __launch_bounds__(kAcBlock) attn_csr_kernel(const AcParams p, co
 #pragma unroll
             for (int c = 0; c < NCH; ++c)
 #pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[j] = __builtin_fmaf(vec_get<VEC>(xv[c], v), vec_get<VEC>(kv[j][c], v), acc[j]);
+                for (int v = 0; v < VEC; ++v) acc[j] = __builtin_fmaf(vec_get<VEC>(xv[c], v), vec_get<VEC>(kv[j][c], v), acc[j]);  // not dot_chain: see there
         }
-        float w4[4], w2[2], w1[1];
-        fold<1, 4>(acc, w4, (lane & 1u) != 0);
-        fold<2, 2>(w4, w2, (lane & 2u) != 0);
-        fold<4, 1>(w2, w1, (lane & 4u) != 0);
-        float s = w1[0];
-        if constexpr (G >= 16) s = s + lane_xor<8>(s);
-        if constexpr (G >= 32) s = s + lane_xor<16>(s);
-        if constexpr (G >= 64) s = s + lane_xor<32>(s);
+        const float s = transpose_sum<G>(acc, lane);
         // lane (any segment, position sub) now holds the score of entry s0 + sub
         const float z = live ? __builtin_fmaf(p.scale, s, b) : ninf;
         float mx = z;
@@ -184,10 +137,10 @@ __global__ void __launch_bounds__(kAcBlock) attn_csr_kernel(const AcParams p, co
         mx = __builtin_fmaxf(mx, lane_xor<4>(mx));
         const float m_new = __builtin_fmaxf(m, mx);
         const float mu_new = __builtin_fabsf(m_new) == __builtin_huge_valf() ? 0.f : m_new;
-        const float alpha = m == ninf ? 1.f : ac_exp(mu - mu_new);
+        const float alpha = m == ninf ? 1.f : lg_exp(mu - mu_new);
         m = m_new;
         mu = mu_new;
-        const float w = ac_exp(z - mu);
+        const float w = lg_exp(z - mu);
         float t = w + lane_xor<1>(w);
         t = t + lane_xor<2>(t);
         t = t + lane_xor<4>(t);
@@ -225,17 +178,11 @@ struct AcCall {
 template <int G, int VEC, int NCH>
 void launch_attn_csr(const AcCall &c) {
     AcParams p = c.p;
-    p.blocks_per_head = ceil_div(p.M, static_cast<uint32_t>(kAcBlock / G));
-    p.total = p.blocks_per_head * c.H;
-    const XcdGrid xg = xcd_grid(p.total);
-    p.xcd_chunk = xg.chunk;
+    const uint32_t grid = finish_grid<G>(p, p.M, c.H);
     note_kernel("attn_csr<f32,G%d,V%d,C%d>", G, VEC, NCH);
-    hipLaunchKernelGGL((attn_csr_kernel<G, VEC, NCH>), dim3(xg.grid), dim3(kAcBlock), 0, c.stream, p, c.rowPtrs, c.colIdxs, c.Q, c.K, c.V,
+    hipLaunchKernelGGL((attn_csr_kernel<G, VEC, NCH>), dim3(grid), dim3(kLgBlock), 0, c.stream, p, c.rowPtrs, c.colIdxs, c.Q, c.K, c.V,
                        c.bias, c.out, c.lse);
 }
-
-// elements one head's rows span: the last row ends with its last column, not with its stride
-uint64_t span(uint64_t rows, uint32_t ld, uint32_t width) { return rows == 0 ? 0 : (rows - 1) * ld + width; }
 
 }  // namespace
 
@@ -248,10 +195,7 @@ extern "C" int mispmm_attn_csr_f32(mispmm_stream_t stream, uint32_t H, uint32_t 
                                    uint64_t k_head_stride, uint32_t ldk, uint32_t D, const float *V, uint64_t v_head_stride, uint32_t ldv,
                                    uint32_t Dv, float scale, const float *bias, uint64_t bias_head_stride, float *out,
                                    uint64_t out_head_stride, uint32_t ldo, float *lse) {
-    if (D == 0 || Dv == 0 || D > kAcMaxWidth || Dv > kAcMaxWidth)
-        return fail(MISPMM_ERR_UNSUPPORTED, "attn_csr_f32: D and Dv must be from 1 to %d (got D=%u Dv=%u)", kAcMaxWidth, D, Dv);
-    if (!(__builtin_fabsf(scale) < __builtin_huge_valf()))
-        return fail(MISPMM_ERR_INVALID_ARG, "attn_csr_f32: scale must be finite (got %g)", static_cast<double>(scale));
+    if (const int st = refuse_shape("attn_csr_f32", D, Dv, scale); st != MISPMM_OK) return st;
     if (H == 0 || M == 0) return MISPMM_OK;
     if (!rowPtrs || !Q || !Kmat || !V || !out || (nnz != 0 && !colIdxs))
         return fail(MISPMM_ERR_INVALID_ARG, "attn_csr_f32: rowPtrs, colIdxs, Q, K, V or out is null");
@@ -271,8 +215,7 @@ extern "C" int mispmm_attn_csr_f32(mispmm_stream_t stream, uint32_t H, uint32_t 
     const int vec = wide ? 4 : 1;
     const uint32_t width = D > Dv ? D : Dv;
     const int g = pick_group(width, vec);
-    if (static_cast<uint64_t>(ceil_div(M, static_cast<uint32_t>(kAcBlock / g))) * H > 0x7FFFFFFFull)
-        return fail(MISPMM_ERR_UNSUPPORTED, "attn_csr_f32: %u rows x %u heads are more workgroups than one launch takes", M, H);
+    if (const int st = refuse_grid("attn_csr_f32", M, H, g); st != MISPMM_OK) return st;
     AcCall c{};
     c.stream = as_stream(stream);
     c.H = H;
@@ -285,13 +228,7 @@ extern "C" int mispmm_attn_csr_f32(mispmm_stream_t stream, uint32_t H, uint32_t 
     p.bias_bytes = static_cast<uint32_t>(bs);
     p.scale = scale;
     p.q_head = q_head_stride, p.k_head = k_head_stride, p.v_head = v_head_stride, p.o_head = out_head_stride, p.bias_head = bias_head_stride;
-    // lanes of a row, elements of a lane, chunks of G * VEC columns: the one list of the instances that exist
-    if (vec == 4) {
-        with_group(g, [&](auto gr) { launch_attn_csr<decltype(gr)::value, 4, 1>(c); });  // 64 x 4 covers 256
-    } else if (!try_const<8, 16, 32>(g, [&](auto gr) { launch_attn_csr<decltype(gr)::value, 1, 1>(c); })) {
-        const uint32_t chunks = ceil_div(width, static_cast<uint32_t>(kWave));
-        with_const<1, 2, 4>(chunks <= 1 ? 1 : chunks == 2 ? 2 : 4, [&](auto ch) { launch_attn_csr<64, 1, decltype(ch)::value>(c); });
-    }
+    with_instance(vec, g, width, [&](auto gr, auto v, auto ch) { launch_attn_csr<decltype(gr)::value, decltype(v)::value, decltype(ch)::value>(c); });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
 }

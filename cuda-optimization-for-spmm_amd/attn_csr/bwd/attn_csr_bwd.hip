@@ -6,11 +6,10 @@
 //   dS[e]  = scale * P[e] * (dP[e] - delta_h[r])
 //   dQ_h[r] = sum over row r of dS[e] K_h[c]      dK_h[c] = sum over column c of dS[e] Q_h[r]  dV_h[c] = sum over column c of P[e] dO_h[r]
 //
-// Shape: both kernels are the lane group of attn_csr/attn_csr.hip turned to a new purpose.  G lanes own one output row, a lane
-// owns VEC consecutive columns of each of NCH chunks of G * VEC, entries are walked in storage order in batches of 8, the two
-// dot products of a batch (s and dP) go through the transposing butterfly so that lane i of every 8-lane segment holds entry
-// i's pair, the exponential and dS are computed once per entry in that lane, and the 8 results come back by a segment
-// broadcast for the accumulating fmas.
+// Shape: both kernels stand on the lane group of attn_csr/lane_group.hpp, as the forward does (G lanes own one output row,
+// batches of 8 entries, the transposing butterfly, the saturating join: explained there).  The two dot products of a batch
+// (s and dP) go through the butterfly so that lane i of every 8-lane segment holds entry i's pair, the exponential and dS are
+// computed once per entry in that lane, and the 8 results come back by a segment broadcast for the accumulating fmas.
 // ROW PASS (A's pattern, a group per (head, row r)): holds Q[r], dO[r] and the dQ accumulator; delta[r] from dO[r] and out[r]
 // before the loop (written by lane 0: the column pass reads it); per batch the K rows and the V rows of the entries' columns;
 // dQ = fma(dS_i, K[c_i], dQ) from the K rows that are in registers already.
@@ -19,53 +18,18 @@
 // three depend on the index that is fetched a batch ahead, so they are issued FIRST at the top of the batch, ahead of the 16
 // row reads: the vector-memory counter is in order and they have arrived when the rows have.
 // s has the same bits in both passes (the same products in the same lane chains and the same tree), hence so do z, P and dS.
-// Dead slots and lanes past a width read through the dropped-load mark joined by the saturating add, as in the forward; a dead
-// slot's P and dS are replaced by +0.  No LDS, no atomics, no scratch; every output row has one owner and a fixed order.
-#include "lane_moves.hpp"
+// A dead slot's P and dS are replaced by +0.  Every output row has one owner and a fixed order.
+#include "../lane_group.hpp"
 #include "mispmm_attn_csr_bwd.h"
 
 namespace mispmm {
 
 namespace {
 
-constexpr int kAbBlock = 256;  // threads per workgroup
-constexpr int kAbBatch = 8;    // entries per step: lane i of an 8-lane segment holds the i-th entry's scalars
-constexpr int kAbMaxWidth = 256;
-
-__device__ __forceinline__ float ab_exp(float t) { return __builtin_amdgcn_exp2f(t * 1.44269504088896340736f); }  // as attn_csr.hip
-
-// key + lane offset where either may be the dropped-load mark: saturating, so that two marks do not wrap to offset 0
-__device__ __forceinline__ uint32_t join_off(uint32_t key, uint32_t off) { return __builtin_elementwise_add_sat(key, off); }
-
-// one step of the transposing butterfly (sddmm.hip): 2 * H values in, H out; the lane whose bit MASK is clear keeps the even ones
-template <int MASK, int H>
-__device__ __forceinline__ void fold(const float *in, float *out, bool odd) {
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        const float keep = odd ? in[2 * j + 1] : in[2 * j];
-        const float send = odd ? in[2 * j] : in[2 * j + 1];
-        out[j] = keep + lane_xor<MASK>(send);
-    }
-}
-
-// the 8 per-lane partial sums of a batch -> the full sum of entry i in lane i of every 8-lane segment of the group
-template <int G>
-__device__ __forceinline__ float transpose_sum(const float *acc, uint32_t lane) {
-    float w4[4], w2[2], w1[1];
-    fold<1, 4>(acc, w4, (lane & 1u) != 0);
-    fold<2, 2>(w4, w2, (lane & 2u) != 0);
-    fold<4, 1>(w2, w1, (lane & 4u) != 0);
-    float s = w1[0];
-    if constexpr (G >= 16) s = s + lane_xor<8>(s);
-    if constexpr (G >= 32) s = s + lane_xor<16>(s);
-    if constexpr (G >= 64) s = s + lane_xor<32>(s);
-    return s;
-}
-
 // P of one entry: exp(z - lse) with one rounding of the difference; a row whose lse is not finite is NaN throughout, as a
 // softmax over a +Inf, a NaN or nothing but -Inf is (z - (+Inf) alone would give +0)
 __device__ __forceinline__ float weight(float z, float lse) {
-    return __builtin_fabsf(lse) < __builtin_huge_valf() ? ab_exp(z - lse) : __builtin_nanf("");
+    return __builtin_fabsf(lse) < __builtin_huge_valf() ? lg_exp(z - lse) : __builtin_nanf("");
 }
 
 struct AbParams {
@@ -85,11 +49,11 @@ struct AbPtrs {
 };
 
 template <int G, int VEC, int NCH>
-__global__ void __launch_bounds__(kAbBlock) attn_csr_bwd_row_kernel(const AbParams p, const AbPtrs a) {
+__global__ void __launch_bounds__(kLgBlock) attn_csr_bwd_row_kernel(const AbParams p, const AbPtrs a) {
     using vec_t = typename VecOf<VEC>::type;
-    static_assert(G >= kAbBatch && (G & (G - 1)) == 0 && G <= kWave, "a batch's scalars sit in the first lanes of a group");
+    static_assert(G >= kLgBatch && (G & (G - 1)) == 0 && G <= kWave, "a batch's scalars sit in the first lanes of a group");
     static_assert(NCH == 1 || G == kWave, "more than one chunk only where a whole wave owns the row");
-    constexpr int GROUPS = kAbBlock / G, E = kAbBatch;
+    constexpr int GROUPS = kLgBlock / G, E = kLgBatch;
     constexpr uint32_t CHUNK = G * VEC;
     const uint32_t lane = threadIdx.x % G, sub = lane & (E - 1);
     const uint32_t item = xcd_block(blockIdx.x, p.xcd_chunk);
@@ -108,9 +72,8 @@ __global__ void __launch_bounds__(kAbBlock) attn_csr_bwd_row_kernel(const AbPara
     float dsum = 0.f;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-        const uint32_t col = c * CHUNK + lane * VEC;
-        koff[c] = col < p.D ? col * 4u : kDropLoad;
-        voff[c] = col < p.Dv ? col * 4u : kDropLoad;
+        koff[c] = lane_off<G, VEC>(lane, c, p.D);
+        voff[c] = lane_off<G, VEC>(lane, c, p.Dv);
         xq[c] = buffer_load_vec<VEC>(qr, join_off(row * p.ldq4, koff[c]), 0);  // past D: zeros
         xg[c] = buffer_load_vec<VEC>(gr, join_off(row * p.ldg4, voff[c]), 0);  // past Dv: zeros
         const vec_t xo = buffer_load_vec<VEC>(orr, join_off(row * p.ldo4, voff[c]), 0);
@@ -168,30 +131,18 @@ __global__ void __launch_bounds__(kAbBlock) attn_csr_bwd_row_kernel(const AbPara
         fetch(s0 + E, nxt_col, nxt_bias);  // on its way while this batch is gathered
         __builtin_amdgcn_sched_barrier(0);  // ... issued here, ahead of the batch's own reads (see the end of the loop body)
         vec_t kv[E][NCH], vv[E][NCH];
-        static_for<0, E>([&](auto j_tag) {
-            constexpr int j = decltype(j_tag)::value;
-            const uint32_t kj = group_bcast<8, j>(kkey);
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) kv[j][c] = buffer_load_vec<VEC>(kr, join_off(kj, koff[c]), 0);
-        });
-        static_for<0, E>([&](auto j_tag) {
-            constexpr int j = decltype(j_tag)::value;
-            const uint32_t vj = group_bcast<8, j>(vkey);
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) vv[j][c] = buffer_load_vec<VEC>(vr, join_off(vj, voff[c]), 0);
-        });
+        gather_rows<VEC, NCH>(kkey, kr, koff, kv);
+        gather_rows<VEC, NCH>(vkey, vr, voff, vv);
         float acc_s[E], acc_p[E];
 #pragma unroll
         for (int j = 0; j < E; ++j) {
             acc_s[j] = 0.f;
             acc_p[j] = 0.f;
 #pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    acc_s[j] = __builtin_fmaf(vec_get<VEC>(xq[c], v), vec_get<VEC>(kv[j][c], v), acc_s[j]);
-                    acc_p[j] = __builtin_fmaf(vec_get<VEC>(xg[c], v), vec_get<VEC>(vv[j][c], v), acc_p[j]);
-                }
+            for (int c = 0; c < NCH; ++c) {
+                acc_s[j] = dot_chain<VEC>(xq[c], kv[j][c], acc_s[j]);
+                acc_p[j] = dot_chain<VEC>(xg[c], vv[j][c], acc_p[j]);
+            }
         }
         const float s = transpose_sum<G>(acc_s, lane);
         const float dp = transpose_sum<G>(acc_p, lane);
@@ -218,11 +169,11 @@ __global__ void __launch_bounds__(kAbBlock) attn_csr_bwd_row_kernel(const AbPara
 }
 
 template <int G, int VEC, int NCH>
-__global__ void __launch_bounds__(kAbBlock) attn_csr_bwd_col_kernel(const AbParams p, const AbPtrs a) {
+__global__ void __launch_bounds__(kLgBlock) attn_csr_bwd_col_kernel(const AbParams p, const AbPtrs a) {
     using vec_t = typename VecOf<VEC>::type;
-    static_assert(G >= kAbBatch && (G & (G - 1)) == 0 && G <= kWave, "a batch's scalars sit in the first lanes of a group");
+    static_assert(G >= kLgBatch && (G & (G - 1)) == 0 && G <= kWave, "a batch's scalars sit in the first lanes of a group");
     static_assert(NCH == 1 || G == kWave, "more than one chunk only where a whole wave owns the row");
-    constexpr int GROUPS = kAbBlock / G, E = kAbBatch;
+    constexpr int GROUPS = kLgBlock / G, E = kLgBatch;
     constexpr uint32_t CHUNK = G * VEC;
     const uint32_t lane = threadIdx.x % G, sub = lane & (E - 1);
     const uint32_t item = xcd_block(blockIdx.x, p.xcd_chunk);
@@ -270,9 +221,8 @@ __global__ void __launch_bounds__(kAbBlock) attn_csr_bwd_col_kernel(const AbPara
     vec_t xk[NCH], xv[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-        const uint32_t col = c * CHUNK + lane * VEC;
-        qoff[c] = col < p.D ? col * 4u : kDropLoad;
-        goff[c] = col < p.Dv ? col * 4u : kDropLoad;
+        qoff[c] = lane_off<G, VEC>(lane, c, p.D);
+        goff[c] = lane_off<G, VEC>(lane, c, p.Dv);
         xk[c] = buffer_load_vec<VEC>(kr, join_off(key * p.ldk4, qoff[c]), 0);  // past D: zeros
         xv[c] = buffer_load_vec<VEC>(vr, join_off(key * p.ldv4, goff[c]), 0);  // past Dv: zeros; read only for dP
     }
@@ -300,26 +250,15 @@ __global__ void __launch_bounds__(kAbBlock) attn_csr_bwd_col_kernel(const AbPara
         const float delta = want_dk ? delta_h[r] : 0.f;
         const float b = buffer_load_vec<1>(br, e_a * 4u, 0);
         vec_t qv[E][NCH], gv[E][NCH];
-        static_for<0, E>([&](auto j_tag) {
-            constexpr int j = decltype(j_tag)::value;
-            const uint32_t qj = group_bcast<8, j>(qkey);
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) qv[j][c] = buffer_load_vec<VEC>(qr, join_off(qj, qoff[c]), 0);
-        });
-        static_for<0, E>([&](auto j_tag) {
-            constexpr int j = decltype(j_tag)::value;
-            const uint32_t gj = group_bcast<8, j>(gkey);
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) gv[j][c] = buffer_load_vec<VEC>(gr, join_off(gj, goff[c]), 0);
-        });
+        gather_rows<VEC, NCH>(qkey, qr, qoff, qv);
+        gather_rows<VEC, NCH>(gkey, gr, goff, gv);
         float acc_s[E];
 #pragma unroll
         for (int j = 0; j < E; ++j) {
             acc_s[j] = 0.f;
 #pragma unroll
             for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc_s[j] = __builtin_fmaf(vec_get<VEC>(qv[j][c], v), vec_get<VEC>(xk[c], v), acc_s[j]);
+                acc_s[j] = dot_chain<VEC>(qv[j][c], xk[c], acc_s[j]);
         }
         const float s = transpose_sum<G>(acc_s, lane);
         const float z = __builtin_fmaf(p.scale, s, b);
@@ -342,8 +281,7 @@ __global__ void __launch_bounds__(kAbBlock) attn_csr_bwd_col_kernel(const AbPara
                 acc_p[j] = 0.f;
 #pragma unroll
                 for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc_p[j] = __builtin_fmaf(vec_get<VEC>(gv[j][c], v), vec_get<VEC>(xv[c], v), acc_p[j]);
+                    acc_p[j] = dot_chain<VEC>(gv[j][c], xv[c], acc_p[j]);
             }
             const float dp = transpose_sum<G>(acc_p, lane);
             float ds = dp - delta;
@@ -374,32 +312,20 @@ struct AbCall {
 template <bool ROW, int G, int VEC, int NCH>
 void launch_pass(const AbCall &c) {
     AbParams p = c.p;
-    p.blocks_per_head = ceil_div(p.N, static_cast<uint32_t>(kAbBlock / G));
-    p.total = p.blocks_per_head * c.H;
-    const XcdGrid xg = xcd_grid(p.total);
-    p.xcd_chunk = xg.chunk;
+    const uint32_t grid = finish_grid<G>(p, p.N, c.H);
     if constexpr (ROW) {
         note_kernel("attn_csr_bwd_row<f32,G%d,V%d,C%d>", G, VEC, NCH);
-        hipLaunchKernelGGL((attn_csr_bwd_row_kernel<G, VEC, NCH>), dim3(xg.grid), dim3(kAbBlock), 0, c.stream, p, c.a);
+        hipLaunchKernelGGL((attn_csr_bwd_row_kernel<G, VEC, NCH>), dim3(grid), dim3(kLgBlock), 0, c.stream, p, c.a);
     } else {
         note_kernel("attn_csr_bwd_col<f32,G%d,V%d,C%d>", G, VEC, NCH);
-        hipLaunchKernelGGL((attn_csr_bwd_col_kernel<G, VEC, NCH>), dim3(xg.grid), dim3(kAbBlock), 0, c.stream, p, c.a);
+        hipLaunchKernelGGL((attn_csr_bwd_col_kernel<G, VEC, NCH>), dim3(grid), dim3(kLgBlock), 0, c.stream, p, c.a);
     }
 }
 
-// lanes of a row, elements of a lane, chunks of G * VEC columns: the one list of the instances that exist, per pass
 template <bool ROW>
 void dispatch_pass(const AbCall &c, int vec, int g, uint32_t width) {
-    if (vec == 4) {
-        with_group(g, [&](auto gr) { launch_pass<ROW, decltype(gr)::value, 4, 1>(c); });  // 64 x 4 covers 256
-    } else if (!try_const<8, 16, 32>(g, [&](auto gr) { launch_pass<ROW, decltype(gr)::value, 1, 1>(c); })) {
-        const uint32_t chunks = ceil_div(width, static_cast<uint32_t>(kWave));
-        with_const<1, 2, 4>(chunks <= 1 ? 1 : chunks == 2 ? 2 : 4, [&](auto ch) { launch_pass<ROW, 64, 1, decltype(ch)::value>(c); });
-    }
+    with_instance(vec, g, width, [&](auto gr, auto v, auto ch) { launch_pass<ROW, decltype(gr)::value, decltype(v)::value, decltype(ch)::value>(c); });
 }
-
-// elements one head's rows span: the last row ends with its last column, not with its stride
-uint64_t span(uint64_t rows, uint32_t ld, uint32_t width) { return rows == 0 ? 0 : (rows - 1) * ld + width; }
 
 struct Extent {
     const char *lo, *hi;
@@ -426,10 +352,7 @@ extern "C" int mispmm_attn_csr_bwd_f32(mispmm_stream_t stream, uint32_t H, uint3
                                        uint64_t g_head_stride, uint32_t ldg, float *delta, float *dQ, uint64_t dq_head_stride,
                                        uint32_t lddq, float *dK, uint64_t dk_head_stride, uint32_t lddk, float *dV,
                                        uint64_t dv_head_stride, uint32_t lddv) {
-    if (D == 0 || Dv == 0 || D > kAbMaxWidth || Dv > kAbMaxWidth)
-        return fail(MISPMM_ERR_UNSUPPORTED, "attn_csr_bwd_f32: D and Dv must be from 1 to %d (got D=%u Dv=%u)", kAbMaxWidth, D, Dv);
-    if (!(__builtin_fabsf(scale) < __builtin_huge_valf()))
-        return fail(MISPMM_ERR_INVALID_ARG, "attn_csr_bwd_f32: scale must be finite (got %g)", static_cast<double>(scale));
+    if (const int st = refuse_shape("attn_csr_bwd_f32", D, Dv, scale); st != MISPMM_OK) return st;
     if (H == 0 || M == 0 || (!dQ && !dK && !dV)) return MISPMM_OK;
     const bool col_pass = (dK || dV) && K != 0;
     const bool row_pass = dQ || (dK && K != 0);  // dK reads delta
@@ -463,9 +386,7 @@ extern "C" int mispmm_attn_csr_bwd_f32(mispmm_stream_t stream, uint32_t H, uint3
     const int vec = wide ? 4 : 1;
     const uint32_t width = D > Dv ? D : Dv;
     const int g = pick_group(width, vec);
-    const uint32_t most = M > K ? M : K;
-    if (static_cast<uint64_t>(ceil_div(most, static_cast<uint32_t>(kAbBlock / g))) * H > 0x7FFFFFFFull)
-        return fail(MISPMM_ERR_UNSUPPORTED, "attn_csr_bwd_f32: %u rows x %u heads are more workgroups than one launch takes", most, H);
+    if (const int st = refuse_grid("attn_csr_bwd_f32", M > K ? M : K, H, g); st != MISPMM_OK) return st;
     // an output must not overlap an input, the workspace or another output
     const Extent ins[] = {extent(Q, H, q_head_stride, qs),           extent(Kmat, H, k_head_stride, ks), extent(V, H, v_head_stride, vs),
                           extent(out, H, out_head_stride, os),       extent(grad_out, H, g_head_stride, gs), extent(bias, H, bias_head_stride, bs),

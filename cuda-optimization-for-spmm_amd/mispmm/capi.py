@@ -164,6 +164,52 @@ def check(status):
         raise MispmmError(status, detail)
 
 
+class SideLibrary:
+    """A library beside libmispmm.so with one header of its own (include/mispmm_*.h), loaded on first use.
+
+    Such a library links the libmispmm.so that lies beside it and leaves its error text and its kernel tag THERE.  check(),
+    last_error() and last_kernel() therefore read both through the handle of the library loaded here -- a lookup through a
+    handle covers the library's own dependencies -- and not through capi.lib(), which MISPMM_LIB may have pointed at another
+    build.  There is no CPU fallback: a missing library raises."""
+
+    # what the linked libmispmm.so answers for the library's calls
+    SHARED = {name: SIGNATURES[name] for name in ("mispmm_last_error", "mispmm_last_kernel", "mispmm_status_string")}
+
+    def __init__(self, soname, env, signatures):
+        self.path = os.environ.get(env) or os.path.join(PKG_DIR, soname)
+        self.signatures = signatures
+        self._lib = None
+
+    def lib(self):
+        """Load the library (once) and attach the signatures.  Raises if it is not built."""
+        if self._lib is None:
+            if not os.path.exists(self.path):
+                raise FileNotFoundError(f"{self.path} is not built -- run `make -C {PKG_DIR}`; mispmm has no CPU fallback")
+            try:
+                import torch  # noqa: F401  torch's HIP runtime first, as in capi.lib()
+            except ImportError:
+                pass
+            handle = ctypes.CDLL(self.path)
+            for name, (restype, argtypes) in {**self.signatures, **self.SHARED}.items():
+                fn = getattr(handle, name)          # AttributeError if the export is missing
+                fn.restype, fn.argtypes = restype, argtypes
+            self._lib = handle
+        return self._lib
+
+    def check(self, status):
+        if status != OK:
+            l = self.lib()
+            detail = l.mispmm_last_error().decode() or l.mispmm_status_string(status).decode()
+            raise MispmmError(status, detail)
+
+    def last_error(self):
+        return self.lib().mispmm_last_error().decode()
+
+    def last_kernel(self):
+        """Tag of the device kernel the calling thread's last compute call enqueued, as the library linked here recorded it."""
+        return self.lib().mispmm_last_kernel().decode()
+
+
 def device_count():
     n = _i(0)
     check(lib().mispmm_device_count(ctypes.byref(n)))

@@ -1,17 +1,11 @@
 """ctypes binding of include/mispmm_bf16.h (libmispmm_bf16.so: the row-list product with B in bf16, a fourth library beside
 libmispmm.so).
 
-libmispmm_bf16.so links the libmispmm.so that lies beside it and leaves its error text and its kernel tag THERE.  check() and
-last_kernel() of this module therefore read both through the handle of the library loaded here -- a lookup through a handle
-covers the library's own dependencies -- and not through capi.lib(), which MISPMM_LIB may have pointed at another build.
-There is no CPU fallback: a missing library raises."""
+Loaded through capi.SideLibrary, which says why check() and last_kernel() go through the library's own handle.
+MISPMM_BF16_LIB points at another build."""
 import ctypes
-import os
 
 from . import capi
-
-PKG_DIR = capi.PKG_DIR
-LIB_PATH = os.environ.get("MISPMM_BF16_LIB") or os.path.join(PKG_DIR, "libmispmm_bf16.so")
 
 _c = ctypes
 _vp, _u32, _i = _c.c_void_p, _c.c_uint32, _c.c_int
@@ -20,45 +14,7 @@ _vp, _u32, _i = _c.c_void_p, _c.c_uint32, _c.c_int
 SIGNATURES = {
     "mispmm_rows_bf16": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _i, _i, _i]),
 }
-# what the linked libmispmm.so answers for this library's calls
-_SHARED = {
-    "mispmm_last_error": (_c.c_char_p, []),
-    "mispmm_last_kernel": (_c.c_char_p, []),
-    "mispmm_status_string": (_c.c_char_p, [_i]),
-}
 
-_lib = None
-
-
-def lib():
-    """Load libmispmm_bf16.so (once) and attach the signatures.  Raises if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise FileNotFoundError(f"{LIB_PATH} is not built -- run `make -C {PKG_DIR}`; mispmm has no CPU fallback")
-        try:
-            import torch  # noqa: F401  torch's HIP runtime first, as in capi.lib()
-        except ImportError:
-            pass
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**SIGNATURES, **_SHARED}.items():
-            fn = getattr(handle, name)          # AttributeError if the export is missing
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
-    return _lib
-
-
-def check(status):
-    if status != capi.OK:
-        l = lib()
-        detail = l.mispmm_last_error().decode() or l.mispmm_status_string(status).decode()
-        raise capi.MispmmError(status, detail)
-
-
-def last_error():
-    return lib().mispmm_last_error().decode()
-
-
-def last_kernel():
-    """Tag of the device kernel the calling thread's last compute call enqueued, as the library linked here recorded it."""
-    return lib().mispmm_last_kernel().decode()
+_side = capi.SideLibrary("libmispmm_bf16.so", "MISPMM_BF16_LIB", SIGNATURES)
+LIB_PATH = _side.path
+lib, check, last_error, last_kernel = _side.lib, _side.check, _side.last_error, _side.last_kernel

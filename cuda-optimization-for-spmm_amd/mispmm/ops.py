@@ -625,6 +625,31 @@ def _attn_csr_operand(t, rows, heads, what):
     return t, ld, (t.stride(0) if t.shape[0] > 1 else 0)
 
 
+def _attn_csr_qkv(a, q, k, v):
+    """_attn_csr_operand of q, k and v for the pattern a: k and v of q's heads, k of q's width."""
+    q3 = _attn_csr_operand(q, a.num_rows, None, "q")
+    heads = q3[0].shape[0]
+    k3 = _attn_csr_operand(k, a.num_cols, heads, "k")
+    v3 = _attn_csr_operand(v, a.num_cols, heads, "v")
+    if k3[0].shape[2] != q3[0].shape[2]:
+        raise ValueError(f"q and k must have the same number of columns, not {q3[0].shape[2]} and {k3[0].shape[2]}")
+    return q3, k3, v3
+
+
+def _attn_csr_bias_head(a, bias, heads):
+    """Head stride of a bias in a's entry order, [nnz] or [H, nnz]; 0: one bias for all heads, or none."""
+    if bias is None:
+        return 0
+    if bias.dtype != torch.float32 or tuple(bias.shape) not in ((a.nnz,), (heads, a.nnz)) or (a.nnz > 1 and bias.stride(-1) != 1):
+        raise ValueError(f"bias must be a float32 tensor of shape ({a.nnz},) or ({heads}, {a.nnz}) with unit stride along the entries, "
+                         f"not {bias.dtype} {tuple(bias.shape)}")
+    if bias.dim() != 2 or heads == 1:
+        return 0
+    if bias.stride(0) < 0:
+        raise ValueError("bias must not have a negative head stride")
+    return bias.stride(0)
+
+
 def attention_csr(a, q, k, v, scale=None, bias=None, return_lse=False, out=None, lse=None, stream=None):
     """Fused attention on a CSR pattern (mispmm_attn_csr_f32, libmispmm_attn_csr.so): for every head, out = softmax over each
     row's stored entries of (scale * <q_r, k_c> + bias), times v -- one launch for all heads, neither the scores nor the
@@ -641,22 +666,9 @@ def attention_csr(a, q, k, v, scale=None, bias=None, return_lse=False, out=None,
     if q.dim() != k.dim() or q.dim() != v.dim():
         raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
     batched = q.dim() == 3
-    q3, ldq, q_head = _attn_csr_operand(q, a.num_rows, None, "q")
-    heads = q3.shape[0]
-    k3, ldk, k_head = _attn_csr_operand(k, a.num_cols, heads, "k")
-    v3, ldv, v_head = _attn_csr_operand(v, a.num_cols, heads, "v")
-    d, dv = q3.shape[2], v3.shape[2]
-    if k3.shape[2] != d:
-        raise ValueError(f"q and k must have the same number of columns, not {d} and {k3.shape[2]}")
-    bias_head = 0
-    if bias is not None:
-        if bias.dtype != torch.float32 or tuple(bias.shape) not in ((a.nnz,), (heads, a.nnz)) or (a.nnz > 1 and bias.stride(-1) != 1):
-            raise ValueError(f"bias must be a float32 tensor of shape ({a.nnz},) or ({heads}, {a.nnz}) with unit stride along the entries, "
-                             f"not {bias.dtype} {tuple(bias.shape)}")
-        if bias.dim() == 2 and heads > 1:
-            bias_head = bias.stride(0)
-            if bias_head < 0:
-                raise ValueError("bias must not have a negative head stride")
+    (q3, ldq, q_head), (k3, ldk, k_head), (v3, ldv, v_head) = _attn_csr_qkv(a, q, k, v)
+    heads, d, dv = q3.shape[0], q3.shape[2], v3.shape[2]
+    bias_head = _attn_csr_bias_head(a, bias, heads)
     if scale is None:
         scale = d ** -0.5
     shape = (heads, a.num_rows, dv)
@@ -713,27 +725,14 @@ def attention_csr_bwd(a, at, perm, q, k, v, out, lse, grad_out, scale=None, bias
     if len({q.dim(), k.dim(), v.dim(), out.dim(), grad_out.dim()}) != 1:
         raise ValueError("q, k, v, out and grad_out must all be 2-D or all [H, ...]")
     batched = q.dim() == 3
-    q3, ldq, q_head = _attn_csr_operand(q, a.num_rows, None, "q")
-    heads = q3.shape[0]
-    k3, ldk, k_head = _attn_csr_operand(k, a.num_cols, heads, "k")
-    v3, ldv, v_head = _attn_csr_operand(v, a.num_cols, heads, "v")
-    d, dvw = q3.shape[2], v3.shape[2]
-    if k3.shape[2] != d:
-        raise ValueError(f"q and k must have the same number of columns, not {d} and {k3.shape[2]}")
+    (q3, ldq, q_head), (k3, ldk, k_head), (v3, ldv, v_head) = _attn_csr_qkv(a, q, k, v)
+    heads, d, dvw = q3.shape[0], q3.shape[2], v3.shape[2]
     o3, ldo, o_head = _attn_csr_result(out, (heads, a.num_rows, dvw), batched, "out")
     g3, ldg, g_head = _attn_csr_result(grad_out, (heads, a.num_rows, dvw), batched, "grad_out")
     rows_shape = (heads, a.num_rows) if batched else (a.num_rows,)
     if lse.dtype != torch.float32 or tuple(lse.shape) != rows_shape or not lse.is_contiguous():
         raise ValueError(f"lse must be a contiguous float32 tensor of shape {rows_shape}")
-    bias_head = 0
-    if bias is not None:
-        if bias.dtype != torch.float32 or tuple(bias.shape) not in ((a.nnz,), (heads, a.nnz)) or (a.nnz > 1 and bias.stride(-1) != 1):
-            raise ValueError(f"bias must be a float32 tensor of shape ({a.nnz},) or ({heads}, {a.nnz}) with unit stride along the entries, "
-                             f"not {bias.dtype} {tuple(bias.shape)}")
-        if bias.dim() == 2 and heads > 1:
-            bias_head = bias.stride(0)
-            if bias_head < 0:
-                raise ValueError("bias must not have a negative head stride")
+    bias_head = _attn_csr_bias_head(a, bias, heads)
     if len(need) != 3:
         raise ValueError("need holds three flags: (dq, dk, dv)")
     if perm is not None:
