@@ -29,9 +29,9 @@ def _dev_f64(a, device):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
 
 
-def _check_dtype(dtype):
+def _check_dtype(dtype, what=None):
     if dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"dtype must be torch.float32 or torch.float64, not {dtype}")
+        raise ValueError(f"{what + ': ' if what else ''}dtype must be torch.float32 or torch.float64, not {dtype}")
     return dtype == torch.float64
 
 
@@ -78,10 +78,68 @@ def check_host(m):
         raise ValueError(f"{type(m).__name__}: data holds {np.asarray(values).size} values, {want} are needed")
 
 
-def _dense_ld(t):
-    if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 and t.shape[1] > 1:
-        raise ValueError("dense operands must be 2-D float32 with unit column stride")
-    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+# ---- the operand contract: what the C ABI cannot see (a dtype, the extent of an allocation, the length of a list) is checked
+# here, once, before any call into a library.  The checks read attributes only: no synchronisation, no allocation, no copy.
+_DENSE_WORDS = {torch.float32: "{what}: dense operands must be 2-D float32 with unit column stride",
+                torch.float64: "{what}: with a float64 A, dense operands must be 2-D float64 with unit column stride",
+                torch.int16: "{what} must be a 2-D int16 tensor of bf16 bits with unit column stride"}
+
+
+def _acc_mode(acc):
+    """The library's number of an accumulation mode given by name."""
+    if acc not in capi.ACC_MODES:
+        raise ValueError(f"acc must be one of {sorted(capi.ACC_MODES)}, not {acc!r}")
+    return capi.ACC_MODES[acc]
+
+
+def _dense(t, what, dtype=torch.float32, rows=None, of="A has {} columns"):
+    """Row stride of a 2-D dense operand of `dtype` with unit column stride, of `rows` rows where given, whose rows do not
+    overlap one another (an expanded tensor's do).  A single row may have any stride."""
+    if t.dim() != 2 or t.dtype != dtype or t.stride(1) != 1 and t.shape[1] > 1:
+        raise ValueError(_DENSE_WORDS[dtype].format(what=what) + f", not {t.dtype} {tuple(t.shape)} with strides {tuple(t.stride())}")
+    if rows is not None and t.shape[0] != rows:
+        raise ValueError(f"{what} has {t.shape[0]} rows, {of.format(rows)}")
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+    if ld < t.shape[1]:
+        raise ValueError(f"{what} must not overlap its own rows (row stride {ld} < {t.shape[1]} columns), e.g. an expanded tensor")
+    return ld
+
+
+def _dense_out(out, m, n, like, dtype=torch.float32, what="out"):
+    """(out, its row stride): `out` checked as an [m, n] result of `dtype`, or a fresh one on like's device."""
+    if out is None:
+        return torch.empty((m, n), dtype=dtype, device=like.device), n
+    _require_gpu(out)
+    if tuple(out.shape) != (m, n):
+        raise ValueError(f"{what} has shape {tuple(out.shape)}, expected {(m, n)}")
+    return out, _dense(out, what, dtype)
+
+
+def _dense_list(ts, what, dtype, rows, of, count=None, cols=None):
+    """Row stride shared by a list of dense operands: EVERY member checked like _dense and against the first one's shape and
+    row stride; `count` members where given, of `cols` columns where given."""
+    if not isinstance(ts, (list, tuple)):
+        raise ValueError(f"{what} must be a list of tensors, not {type(ts).__name__}")
+    if count is not None and len(ts) != count:
+        raise ValueError(f"{what} holds {len(ts)} tensors, {count} are needed: one per operand")
+    ld0 = None
+    for i, t in enumerate(ts):
+        _require_gpu(t)
+        ld = _dense(t, f"{what}[{i}]", dtype, rows, of)
+        if ld0 is None:
+            ld0 = ld
+        if t.shape != ts[0].shape or ld != ld0:
+            raise ValueError(f"{what}[{i}]: batched operands must share one shape and row stride")
+        if cols is not None and t.shape[1] != cols:
+            raise ValueError(f"{what}[{i}] has {t.shape[1]} columns, expected {cols}")
+    return ld0
+
+
+def _flat(t, what, dtype, count, exact=True):
+    """t as a contiguous array of `count` elements of `dtype` (at least `count` with exact=False), whatever its shape."""
+    if t.dtype != dtype or not t.is_contiguous() or (t.numel() != count if exact else t.numel() < count):
+        raise ValueError(f"{what} must be a contiguous {dtype} tensor of {'' if exact else 'at least '}{count} elements, not {t.dtype} "
+                         f"{tuple(t.shape)} with strides {tuple(t.stride())}")
 
 
 def uniform_row_nnz(row_ptrs):
@@ -202,7 +260,9 @@ def autotune_pick(times_us, min_gain=0.02):
 def use_plan(a, n, acc="reference", stream=None):
     """Plan order or storage order for a product of `a` with a dense operand of n columns: MEASURED on the first product of that
     width (mispmm_csr_autotune_plan_f32: both candidates timed on scratch operands, ~1-2 ms) and remembered in a.tuned; the
-    footprint rule where it cannot be measured (stream being captured, autotune switched off, MISPMM_PLAN_MIN_N given)."""
+    footprint rule where it cannot be measured (stream being captured, autotune switched off, MISPMM_PLAN_MIN_N given).
+    a: a float32 DeviceCSR; acc: "reference" or "fast"."""
+    mode = _acc_mode(acc)
     if a.plan is None:
         return False
     if PLAN_MIN_N is not None or not AUTOTUNE:
@@ -213,7 +273,7 @@ def use_plan(a, n, acc="reference", stream=None):
         use, times = ctypes.c_int(0), (ctypes.c_float * 2)()
         st = capi.lib().mispmm_csr_autotune_plan_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs), _p(a.data),
                                                      a.uniform_row_nnz, _p(p.row_ptrs), _p(p.col_idxs), _p(p.data), _p(p.row_map), int(n),
-                                                     capi.ACC_MODES[acc], 0, ctypes.byref(use), times)
+                                                     mode, 0, ctypes.byref(use), times)
         if st != capi.OK:                       # e.g. the stream is being captured: nothing measured, nothing remembered
             return plan_pays(a.num_cols, n)
         a.tuned[key] = (bool(use.value), (float(times[0]), float(times[1])))
@@ -348,16 +408,19 @@ def _rows_split(rs, num_rows, num_cols, nnz, col_idxs, data, b, c, acc, stream):
     allow it; False = take the format's own entry point."""
     if rs is None:
         return False
+    mode = _acc_mode(acc)
+    ldb = _dense(b, "b", rows=num_cols)
+    _, ldc = _dense_out(c, num_rows, b.shape[1], b)
     if 0 < rs.long_spans < num_rows and os.environ.get("MISPMM_NO_HYBRID") != "1":
         st = capi.lib().mispmm_rows_hybrid_f32(_stream_ptr(stream), num_rows, num_cols, nnz, _p(col_idxs), _p(data), _p(rs.spans), num_rows,
-                                               rs.long_spans, _p(b), b.shape[1], _dense_ld(b), _p(c), _dense_ld(c), capi.ACC_MODES[acc])
+                                               rs.long_spans, _p(b), b.shape[1], ldb, _p(c), ldc, mode)
         if st != capi.ERR_UNSUPPORTED:
             capi.check(st)
             return True
     if rs.hybrid_only:
         return False
     st = capi.lib().mispmm_rows_split_f32(_stream_ptr(stream), num_rows, num_cols, nnz, _p(col_idxs), _p(data), _p(rs.spans), num_rows,
-                                          _p(b), b.shape[1], _dense_ld(b), _p(c), _dense_ld(c), capi.ACC_MODES[acc])
+                                          _p(b), b.shape[1], ldb, _p(c), ldc, mode)
     if st == capi.ERR_UNSUPPORTED:
         return False
     capi.check(st)
@@ -395,19 +458,14 @@ class DeviceCOO:
                          _dev_u32(coo.col_idxs[order], device), _dev_f32(coo.data[order], device), _row_spans(row_ptrs, device))
 
 
-def _out(m, n, b, out, dtype=torch.float32):
-    if out is None:
-        out = torch.empty((m, n), dtype=dtype, device=b.device)
-    _require_gpu(out)
-    if out.shape != (m, n):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(m, n)}")
-    return out
-
-
-def _dense_ld_f64(t):
-    if t.dim() != 2 or t.dtype != torch.float64 or t.stride(1) != 1 and t.shape[1] > 1:
-        raise ValueError("with a float64 A, dense operands must be 2-D float64 with unit column stride")
-    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+def _b_and_out(b, out, num_rows, num_cols, acc, dtype=torch.float32):
+    """(N, ldb, C, ldc, mode) of C = A @ B for an A of num_rows x num_cols: b and out checked as the dense operands of
+    `dtype` every product takes, acc by name."""
+    mode = _acc_mode(acc)
+    ldb = _dense(b, "b", dtype, num_cols)
+    n = b.shape[1]
+    c, ldc = _dense_out(out, num_rows, n, b, dtype)
+    return n, ldb, c, ldc, mode
 
 
 def _spmm_rows_f64(num_rows, num_cols, nnz, row_ptrs, col_idxs, data, b, out, kernel, acc, stream):
@@ -415,50 +473,42 @@ def _spmm_rows_f64(num_rows, num_cols, nnz, row_ptrs, col_idxs, data, b, out, ke
     order, bit-exact against the reference's CPU functions with DT = double)."""
     if int(kernel) != 0:
         raise ValueError("float64 operands have one kernel: kernel must be 0")
-    if b.shape[0] != num_cols:
-        raise ValueError(f"B has {b.shape[0]} rows, A has {num_cols} columns")
-    ldb = _dense_ld_f64(b)
-    n = b.shape[1]
-    c = _out(num_rows, n, b, out, torch.float64)
-    ldc = _dense_ld_f64(c)
+    n, ldb, c, ldc, mode = _b_and_out(b, out, num_rows, num_cols, acc, torch.float64)
     capi.check(capi.lib().mispmm_csr_f64(_stream_ptr(stream), num_rows, num_cols, nnz, _p(row_ptrs), _p(col_idxs), _p(data), _p(b), n, ldb,
-                                         _p(c), ldc, capi.ACC_MODES[acc]))
+                                         _p(c), ldc, mode))
     return c
 
 
 def spmm_csr(a, b, out=None, kernel=0, acc="reference", stream=None, use_hint=True):
-    """C = A @ B.  a: DeviceCSR, b: [K, N] float32 device tensor (row-major, any row stride).
+    """C = A @ B.  a: DeviceCSR, b: [K, N] float32 device tensor, out: [M, N] float32 where given -- both row-major with unit
+    column stride and any row stride of at least N (the corner of a larger buffer; a single row may have any stride).
+    acc: "reference" or "fast".
     With the default kernel (0 / 5) a CSR whose rows all have the same length goes through
     mispmm_csr_uniform_f32 (no row-pointer fetch), one that carries `spans` (long rows) through mispmm_csr_split_f32 with
     its rows longest first; use_hint=False forces the general entry point.
     A float64 A (DeviceCSR.from_host(..., dtype=torch.float64)) takes mispmm_csr_f64: B and out float64, kernel 0."""
-    _require_gpu(a.row_ptrs, b)
+    _require_gpu(a.row_ptrs, b, out)
     if a.data.dtype == torch.float64:
         return _spmm_rows_f64(a.num_rows, a.num_cols, a.nnz, a.row_ptrs, a.col_idxs, a.data, b, out, kernel, acc, stream)
-    if b.shape[0] != a.num_cols:
-        raise ValueError(f"B has {b.shape[0]} rows, A has {a.num_cols} columns")
-    n = b.shape[1]
-    c = _out(a.num_rows, n, b, out)
+    n, ldb, c, ldc, mode = _b_and_out(b, out, a.num_rows, a.num_cols, acc)
     hints = use_hint and os.environ.get("MISPMM_NO_HINT") != "1"
     if hints and a.plan is not None and int(kernel) in (0, 5) and use_plan(a, n, acc, stream):
         # rows in the clustered order of the plan (same bits: every row keeps its entries in storage order)
-        if _csr_plan(a, [b], [c], acc, stream):
+        if _csr_plan_launch(a, [b], [c], n, ldb, ldc, mode, stream):
             return c
-    if use_hint and os.environ.get("MISPMM_NO_HINT") != "1" and a.uniform_row_nnz and int(kernel) in (0, 5) and a.num_cols * _dense_ld(b) * 4 <= 0x7FFFFFFF:
+    if hints and a.uniform_row_nnz and int(kernel) in (0, 5) and a.num_cols * ldb * 4 <= 0x7FFFFFFF:
         capi.check(capi.lib().mispmm_csr_uniform_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.uniform_row_nnz,
-                                                     _p(a.col_idxs), _p(a.data), _p(b), n, _dense_ld(b), _p(c),
-                                                     _dense_ld(c), capi.ACC_MODES[acc]))
+                                                     _p(a.col_idxs), _p(a.data), _p(b), n, ldb, _p(c), ldc, mode))
         return c
     # the split kernel with the rows longest first: kernel 6 always, kernel 0 / 5 where the library itself would split
     # (REFERENCE mode: up to 383 columns)
     wants_split = int(kernel) == 6 or (int(kernel) in (0, 5) and (acc == "fast" or n < 384))
-    if use_hint and os.environ.get("MISPMM_NO_HINT") != "1" and a.spans is not None and wants_split:
+    if hints and a.spans is not None and wants_split:
         # kernel 0 / 5: the long rows by the split body and the short rows by the row-gather body of ONE launch, where the
         # shape has such a launch (else, and for kernel 6 by name, the split kernel on the whole list)
         if int(kernel) != 6 and 0 < a.long_spans < a.spans.numel() // 4 and os.environ.get("MISPMM_NO_HYBRID") != "1":
             st = capi.lib().mispmm_csr_hybrid_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.nnz, _p(a.col_idxs), _p(a.data),
-                                                  _p(a.spans), a.spans.numel() // 4, a.long_spans, _p(b), n, _dense_ld(b), _p(c),
-                                                  _dense_ld(c), capi.ACC_MODES[acc])
+                                                  _p(a.spans), a.spans.numel() // 4, a.long_spans, _p(b), n, ldb, _p(c), ldc, mode)
             if st != capi.ERR_UNSUPPORTED:
                 capi.check(st)
                 return c
@@ -466,48 +516,63 @@ def spmm_csr(a, b, out=None, kernel=0, acc="reference", stream=None, use_hint=Tr
             st = capi.ERR_UNSUPPORTED        # short rows on average: the wave-per-row split kernel is not for this matrix
         else:
             st = capi.lib().mispmm_csr_split_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs),
-                                                 _p(a.data), _p(a.spans), a.spans.numel() // 4, _p(b), n, _dense_ld(b), _p(c),
-                                                 _dense_ld(c), capi.ACC_MODES[acc])
+                                                 _p(a.data), _p(a.spans), a.spans.numel() // 4, _p(b), n, ldb, _p(c), ldc, mode)
         if st != capi.ERR_UNSUPPORTED:  # operands that are not 16-byte vectors take the general entry point below
             capi.check(st)
             return c
     capi.check(capi.lib().mispmm_csr_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs),
-                                         _p(a.col_idxs), _p(a.data), _p(b), n, _dense_ld(b), _p(c), _dense_ld(c),
-                                         int(kernel), capi.ACC_MODES[acc]))
+                                         _p(a.col_idxs), _p(a.data), _p(b), n, ldb, _p(c), ldc, int(kernel), mode))
     return c
 
 
-def _csr_plan(a, bs, cs, acc, stream):
-    """mispmm_csr_plan_f32 over the plan's arrays; False = the shape is not taken (B of 2 GiB or more)."""
+def _batch_operands(a, bs, cs, acc, what):
+    """(N, ldb, ldc, mode) of cs[i] = A @ bs[i]: both lists checked member by member (float32, A's rows or columns, unit column
+    stride, no overlapping rows, one shape and one row stride per list, on the device) and of one length."""
+    mode = _acc_mode(acc)
+    ldb = _dense_list(bs, "bs", torch.float32, a.num_cols, "A has {} columns")
+    n = bs[0].shape[1]
+    ldc = _dense_list(cs, what, torch.float32, a.num_rows, "A has {} rows", count=len(bs), cols=n)
+    return n, ldb, ldc, mode
+
+
+def _csr_plan_launch(a, bs, cs, n, ldb, ldc, mode, stream):
     p = a.plan
     blist = (ctypes.c_void_p * len(bs))(*[b.data_ptr() for b in bs])
     clist = (ctypes.c_void_p * len(bs))(*[c.data_ptr() for c in cs])
     st = capi.lib().mispmm_csr_plan_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.nnz, _p(p.row_ptrs), _p(p.col_idxs), _p(p.data),
-                                        a.uniform_row_nnz, _p(p.row_map), len(bs), blist, bs[0].shape[1], _dense_ld(bs[0]), clist,
-                                        _dense_ld(cs[0]), capi.ACC_MODES[acc])
+                                        a.uniform_row_nnz, _p(p.row_map), len(bs), blist, n, ldb, clist, ldc, mode)
     if st == capi.ERR_UNSUPPORTED:
         return False
     capi.check(st)
     return True
 
 
+def _csr_plan(a, bs, cs, acc, stream):
+    """mispmm_csr_plan_f32 over the plan's arrays; False = the shape is not taken (B of 2 GiB or more).  a: a DeviceCSR that
+    carries a plan; bs: a non-empty list of [K, N] float32 device tensors of one shape and row stride; cs: as many [M, N]
+    ones."""
+    _require_gpu(a.row_ptrs)
+    if a.plan is None or not bs:
+        raise ValueError("_csr_plan takes a DeviceCSR with a plan and at least one operand in bs")
+    return _csr_plan_launch(a, bs, cs, *_batch_operands(a, bs, cs, acc, "cs"), stream)
+
+
 def spmm_csr_batch(a, bs, outs=None, acc="reference", stream=None):
     """outs[i] = A @ bs[i] for a list of equally shaped dense operands, ONE launch per 16 of them
-    (mispmm_csr_batch_f32).  Returns the list of results."""
+    (mispmm_csr_batch_f32).  Returns the list of results.  a: a float32 DeviceCSR; bs: a list of [K, N] float32 device
+    tensors that share one shape and one row stride (unit column stride, rows that do not overlap); outs, where given: a list
+    of as many [M, N] float32 tensors, again of one row stride."""
     if not bs:
         return []
+    _require_gpu(a.row_ptrs)
     if a.data.dtype == torch.float64:
         raise ValueError("spmm_csr_batch multiplies float32 operands only; multiply a float64 A with spmm_csr")
-    n, ldb = bs[0].shape[1], _dense_ld(bs[0])
-    for b in bs:
-        _require_gpu(b)
-        if b.shape != bs[0].shape or _dense_ld(b) != ldb:
-            raise ValueError("batched operands must share one shape and row stride")
-        if b.shape[0] != a.num_cols:
-            raise ValueError(f"B has {b.shape[0]} rows, A has {a.num_cols} columns")
     if outs is None:
+        mode, ldb = _acc_mode(acc), _dense_list(bs, "bs", torch.float32, a.num_cols, "A has {} columns")
+        n = ldc = bs[0].shape[1]
         outs = [torch.empty((a.num_rows, n), dtype=torch.float32, device=bs[0].device) for _ in bs]
-    ldc = _dense_ld(outs[0])
+    else:
+        n, ldb, ldc, mode = _batch_operands(a, bs, outs, acc, "outs")
     if a.spans is not None:
         # long rows: the library issues one launch per operand anyway (there is no batched split kernel); go through the
         # span list like spmm_csr does, so that both give the same bits in FAST mode as well
@@ -515,13 +580,12 @@ def spmm_csr_batch(a, bs, outs=None, acc="reference", stream=None):
             spmm_csr(a, b, out=c, acc=acc, stream=stream)
         return outs
     if a.plan is not None and os.environ.get("MISPMM_NO_HINT") != "1" and use_plan(a, n, acc, stream):
-        if _csr_plan(a, bs, outs, acc, stream):
+        if _csr_plan_launch(a, bs, outs, n, ldb, ldc, mode, stream):
             return outs
     blist = (ctypes.c_void_p * len(bs))(*[b.data_ptr() for b in bs])
     clist = (ctypes.c_void_p * len(bs))(*[c.data_ptr() for c in outs])
     capi.check(capi.lib().mispmm_csr_batch_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs),
-                                               _p(a.data), a.uniform_row_nnz, len(bs), blist, n, ldb, clist, ldc,
-                                               capi.ACC_MODES[acc]))
+                                               _p(a.data), a.uniform_row_nnz, len(bs), blist, n, ldb, clist, ldc, mode))
     return outs
 
 
@@ -544,9 +608,11 @@ def sddmm_csr(a, x, y, out=None, acc="reference", stream=None):
     dense-dense product on A's pattern, A's values unread.  a: DeviceCSR [M x K]; x: [M, N], y: [K, N] device tensors of one
     dtype (float32 or float64; row-major, any row stride); returns a tensor of nnz elements in A's storage order."""
     _require_gpu(a.row_ptrs, x, y, out)
-    f64 = _check_dtype(x.dtype)
-    ld = _dense_ld_f64 if f64 else _dense_ld
-    ldx, ldy = ld(x), ld(y)
+    f64 = _check_dtype(x.dtype, "x")
+    mode = _acc_mode(acc)
+    if y.dtype != x.dtype:
+        raise ValueError(f"x and y must be of one dtype, not {x.dtype} and {y.dtype}")
+    ldx, ldy = _dense(x, "x", x.dtype), _dense(y, "y", x.dtype)
     if x.shape[0] != a.num_rows or y.shape[0] != a.num_cols or x.shape[1] != y.shape[1]:
         raise ValueError(f"A is {a.num_rows} x {a.num_cols}: x must be [{a.num_rows}, N] and y [{a.num_cols}, N], not "
                          f"{tuple(x.shape)} and {tuple(y.shape)}")
@@ -556,7 +622,7 @@ def sddmm_csr(a, x, y, out=None, acc="reference", stream=None):
         raise ValueError(f"out must be a contiguous {x.dtype} tensor of {a.nnz} elements")
     fn = capi.lib().mispmm_sddmm_csr_f64 if f64 else capi.lib().mispmm_sddmm_csr_f32
     capi.check(fn(_stream_ptr(stream), a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs), _p(x), ldx, _p(y), ldy,
-                  x.shape[1], _p(out), capi.ACC_MODES[acc]))
+                  x.shape[1], _p(out), mode))
     return out
 
 
@@ -572,7 +638,8 @@ def softmax_csr(a, scores, out=None, acc="reference", stream=None):
     only row_ptrs, num_rows and nnz are used; scores: nnz elements in A's storage order, float32 or float64.  A -Inf score is
     a masked entry (+0); a row with a NaN, a +Inf or nothing but -Inf is NaN throughout.  out may be scores itself."""
     _require_gpu(a.row_ptrs, scores, out)
-    f64 = _check_dtype(scores.dtype)
+    f64 = _check_dtype(scores.dtype, "scores")
+    mode = _acc_mode(acc)
     _entries(a, scores, "scores")
     if out is None:
         out = torch.empty_like(scores)
@@ -580,7 +647,7 @@ def softmax_csr(a, scores, out=None, acc="reference", stream=None):
         raise ValueError(f"out must be {scores.dtype}, like scores")
     _entries(a, out, "out")
     fn = capi.lib().mispmm_softmax_csr_f64 if f64 else capi.lib().mispmm_softmax_csr_f32
-    capi.check(fn(_stream_ptr(stream), a.num_rows, a.nnz, _p(a.row_ptrs), _p(scores), _p(out), capi.ACC_MODES[acc]))
+    capi.check(fn(_stream_ptr(stream), a.num_rows, a.nnz, _p(a.row_ptrs), _p(scores), _p(out), mode))
     return out
 
 
@@ -588,7 +655,8 @@ def softmax_csr_bwd(a, p, dp, out=None, acc="reference", stream=None):
     """ds[e] = p[e] * (dp[e] - sum over row r of p[e'] * dp[e']) (mispmm_softmax_csr_bwd_f32 / _f64): the gradient of
     softmax_csr with respect to the scores, given its result p and the gradient dp of that result.  out may be dp itself."""
     _require_gpu(a.row_ptrs, p, dp, out)
-    f64 = _check_dtype(p.dtype)
+    f64 = _check_dtype(p.dtype, "p")
+    mode = _acc_mode(acc)
     if dp.dtype != p.dtype:
         raise ValueError(f"dp must be {p.dtype}, like p")
     _entries(a, p, "p")
@@ -599,7 +667,7 @@ def softmax_csr_bwd(a, p, dp, out=None, acc="reference", stream=None):
         raise ValueError(f"out must be {p.dtype}, like p")
     _entries(a, out, "out")
     fn = capi.lib().mispmm_softmax_csr_bwd_f64 if f64 else capi.lib().mispmm_softmax_csr_bwd_f32
-    capi.check(fn(_stream_ptr(stream), a.num_rows, a.nnz, _p(a.row_ptrs), _p(p), _p(dp), _p(out), capi.ACC_MODES[acc]))
+    capi.check(fn(_stream_ptr(stream), a.num_rows, a.nnz, _p(a.row_ptrs), _p(p), _p(dp), _p(out), mode))
     return out
 
 
@@ -809,15 +877,13 @@ class DeviceCSRTiles:
 
 
 def spmm_csr_tiles(a, b, out=None, acc="reference", stream=None):
-    """C = A @ B with the B rows of every tile staged in LDS (mispmm_csr_lds_tile_f32): a: DeviceCSRTiles."""
+    """C = A @ B with the B rows of every tile staged in LDS (mispmm_csr_lds_tile_f32): a: DeviceCSRTiles; b, out and
+    acc as spmm_csr takes them (float32, unit column stride, any row stride of at least N)."""
     _require_gpu(a.tile_row_ptrs, b)
-    if b.shape[0] != a.num_cols:
-        raise ValueError(f"B has {b.shape[0]} rows, A has {a.num_cols} columns")
-    n = b.shape[1]
-    c = _out(a.num_rows, n, b, out)
+    n, ldb, c, ldc, mode = _b_and_out(b, out, a.num_rows, a.num_cols, acc)
     capi.check(capi.lib().mispmm_csr_lds_tile_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.row_nnz, a.num_tiles, a.max_tile_cols,
                                                   _p(a.tile_row_ptrs), _p(a.tile_col_ptrs), _p(a.tile_cols), _p(a.slots), _p(a.data),
-                                                  _p(a.row_map), _p(b), n, _dense_ld(b), _p(c), _dense_ld(c), capi.ACC_MODES[acc]))
+                                                  _p(a.row_map), _p(b), n, ldb, _p(c), ldc, mode))
     return c
 
 
@@ -854,52 +920,49 @@ class DeviceCSRPanels:
 
 
 def spmm_csr_panels(a, b, out=None, acc="reference", stream=None):
-    """C = A @ B with B staged panel by panel in LDS (mispmm_csr_panel_f32, for dense-regime A): a: DeviceCSRPanels."""
+    """C = A @ B with B staged panel by panel in LDS (mispmm_csr_panel_f32, for dense-regime A): a: DeviceCSRPanels; b, out
+    and acc as spmm_csr takes them (float32, unit column stride, any row stride of at least N)."""
     _require_gpu(a.panel_ptrs, b)
-    if b.shape[0] != a.num_cols:
-        raise ValueError(f"B has {b.shape[0]} rows, A has {a.num_cols} columns")
-    n = b.shape[1]
-    c = _out(a.num_rows, n, b, out)
+    n, ldb, c, ldc, mode = _b_and_out(b, out, a.num_rows, a.num_cols, acc)
     capi.check(capi.lib().mispmm_csr_panel_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs),
-                                               _p(a.data), _p(a.panel_ptrs), a.panel_rows, _p(b), n, _dense_ld(b), _p(c), _dense_ld(c),
-                                               capi.ACC_MODES[acc]))
+                                               _p(a.data), _p(a.panel_ptrs), a.panel_rows, _p(b), n, ldb, _p(c), ldc,
+                                               mode))
     return c
 
 
 def spmm_ell(a, b, out=None, kernel=0, acc="reference", stream=None):
+    """C = A @ B for a DeviceELL (mispmm_ell_f32; the list of occupied slots where the upload made one).  b, out and acc as
+    spmm_csr takes them: [K, N] and [M, N] float32, unit column stride, any row stride of at least N.  A float64 A takes
+    mispmm_csr_f64: B and out float64, kernel 0."""
     _require_gpu(a.col_idxs, b)
     if a.data.dtype == torch.float64:
         nnz, rp, ci, va, _ = a.compact
         return _spmm_rows_f64(a.num_rows, a.num_cols, nnz, rp, ci, va, b, out, kernel, acc, stream)
-    if b.shape[0] != a.num_cols:
-        raise ValueError(f"B has {b.shape[0]} rows, A has {a.num_cols} columns")
-    n = b.shape[1]
-    c = _out(a.num_rows, n, b, out)
+    n, ldb, c, ldc, mode = _b_and_out(b, out, a.num_rows, a.num_cols, acc)
     if a.compact is not None and int(kernel) in (0, 1):   # mostly padding: multiply from the list of occupied slots
         nnz, rp, ci, va, spans = a.compact
         if _rows_split(spans, a.num_rows, a.num_cols, nnz, ci, va, b, c, acc, stream):
             return c
         st = capi.lib().mispmm_ell_compact_f32(_stream_ptr(stream), a.num_rows, a.num_cols, nnz, _p(rp), _p(ci), _p(va), _p(b), n,
-                                               _dense_ld(b), _p(c), _dense_ld(c), capi.ACC_MODES[acc])
+                                               ldb, _p(c), ldc, mode)
         if st != capi.ERR_UNSUPPORTED:
             capi.check(st)
             return c
     capi.check(capi.lib().mispmm_ell_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.width, _p(a.col_idxs),
-                                         _p(a.data), _p(b), n, _dense_ld(b), _p(c), _dense_ld(c), int(kernel),
-                                         capi.ACC_MODES[acc]))
+                                         _p(a.data), _p(b), n, ldb, _p(c), ldc, int(kernel),
+                                         mode))
     return c
 
 
 def spmm_bsr(a, b, out=None, kernel=0, acc="reference", stream=None):
+    """C = A @ B for a DeviceBSR of float32 blocks (mispmm_bsr_f32).  b, out and acc as spmm_csr takes them: [K, N] and [M, N]
+    float32, unit column stride, any row stride of at least N."""
     _require_gpu(a.block_row_ptrs, b)
-    if b.shape[0] != a.num_cols:
-        raise ValueError(f"B has {b.shape[0]} rows, A has {a.num_cols} columns")
-    n = b.shape[1]
-    c = _out(a.num_rows, n, b, out)
+    n, ldb, c, ldc, mode = _b_and_out(b, out, a.num_rows, a.num_cols, acc)
     capi.check(capi.lib().mispmm_bsr_f32(_stream_ptr(stream), a.num_rows // a.block_row_size, a.num_cols,
                                          a.block_row_size, a.block_col_size, a.num_blocks, _p(a.block_row_ptrs),
-                                         _p(a.block_col_idxs), _p(a.data), _p(b), n, _dense_ld(b), _p(c), _dense_ld(c),
-                                         int(kernel), capi.ACC_MODES[acc]))
+                                         _p(a.block_col_idxs), _p(a.data), _p(b), n, ldb, _p(c), ldc,
+                                         int(kernel), mode))
     return c
 
 
@@ -931,19 +994,16 @@ def bsr_nonzeros(bsr, device="cuda", dtype=torch.float32, check=True):
 
 def spmm_bsr_nonzeros(nz, b, out=None, acc="reference", stream=None):
     """C = A @ B from the non-zero list of a BSR (bsr_nonzeros): fp32 product, fp32 add in the reference's order.  A float64
-    list takes mispmm_csr_f64: B and out float64."""
+    list takes mispmm_csr_f64: B and out float64.  b, out and acc as spmm_csr takes them."""
     _require_gpu(nz.row_ptrs, b)
     if nz.data.dtype == torch.float64:
         return _spmm_rows_f64(nz.num_rows, nz.num_cols, nz.nnz, nz.row_ptrs, nz.col_idxs, nz.data, b, out, 0, acc, stream)
-    if b.shape[0] != nz.num_cols:
-        raise ValueError(f"B has {b.shape[0]} rows, A has {nz.num_cols} columns")
-    n = b.shape[1]
-    c = _out(nz.num_rows, n, b, out)
+    n, ldb, c, ldc, mode = _b_and_out(b, out, nz.num_rows, nz.num_cols, acc)
     if _rows_split(nz.spans, nz.num_rows, nz.num_cols, nz.nnz, nz.col_idxs, nz.data, b, c, acc, stream):
         return c
     capi.check(capi.lib().mispmm_bsr_nonzeros_f32(_stream_ptr(stream), nz.num_rows, nz.num_cols, nz.nnz, _p(nz.row_ptrs),
-                                                  _p(nz.col_idxs), _p(nz.data), _p(b), n, _dense_ld(b), _p(c), _dense_ld(c),
-                                                  capi.ACC_MODES[acc]))
+                                                  _p(nz.col_idxs), _p(nz.data), _p(b), n, ldb, _p(c), ldc,
+                                                  mode))
     return c
 
 
@@ -957,30 +1017,33 @@ def coo_row_bounds(a, stream=None):
 
 def spmm_coo(a, b, out=None, kernel=0, acc="reference", stream=None, workspace=True):
     """workspace=True allocates the (M+1)-entry row-boundary scratch; False uses binary search; a tensor from
-    coo_row_bounds() is used as is (pass kernel=2 to skip rebuilding it).  A float64 A takes mispmm_csr_f64 over its row
+    coo_row_bounds() is used as is (pass kernel=2 to skip rebuilding it): a contiguous int32 device tensor of at least M + 1
+    elements, which the kernel writes.  b, out, acc: as in spmm_csr.  A float64 A takes mispmm_csr_f64 over its row
     boundaries: B and out float64, kernel 0."""
-    _require_gpu(a.row_idxs, b)
+    _require_gpu(a.row_idxs, b, out)
     if a.data.dtype == torch.float64:
         return _spmm_rows_f64(a.num_rows, a.num_cols, a.nnz, a.row_bounds, a.col_idxs, a.data, b, out, kernel, acc, stream)
+    n, ldb, c, ldc, mode = _b_and_out(b, out, a.num_rows, a.num_cols, acc)
     if isinstance(workspace, torch.Tensor):
+        _require_gpu(workspace)
+        _flat(workspace, "workspace", torch.int32, a.num_rows + 1, exact=False)
         ws = workspace
     else:
         ws = torch.empty(a.num_rows + 1, dtype=torch.int32, device=b.device) if workspace else None
-    if b.shape[0] != a.num_cols:
-        raise ValueError(f"B has {b.shape[0]} rows, A has {a.num_cols} columns")
-    n = b.shape[1]
-    c = _out(a.num_rows, n, b, out)
     if workspace is not False and int(kernel) in (0, 1, 2) and _rows_split(a.spans, a.num_rows, a.num_cols, a.nnz, a.col_idxs, a.data, b, c, acc, stream):
         return c
     capi.check(capi.lib().mispmm_coo_f32(_stream_ptr(stream), a.num_rows, a.num_cols, a.nnz, _p(a.row_idxs),
-                                         _p(a.col_idxs), _p(a.data), _p(b), n, _dense_ld(b), _p(c), _dense_ld(c),
-                                         _p(ws), int(kernel), capi.ACC_MODES[acc]))
+                                         _p(a.col_idxs), _p(a.data), _p(b), n, ldb, _p(c), ldc,
+                                         _p(ws), int(kernel), mode))
     return c
 
 
 def f32_to_bf16(x, stream=None):
-    """Device fp32 tensor -> int16 tensor of bf16 bit patterns (round to nearest even)."""
+    """Device fp32 tensor -> int16 tensor of bf16 bit patterns (round to nearest even).  x: float32 of any shape; a view that
+    is not contiguous is copied first."""
     _require_gpu(x)
+    if x.dtype != torch.float32:
+        raise ValueError(f"x must be a float32 tensor, not {x.dtype}")
     x = x.contiguous()
     out = torch.empty(x.shape, dtype=torch.int16, device=x.device)
     capi.check(capi.lib().mispmm_f32_to_bf16(_stream_ptr(stream), x.numel(), _p(x), _p(out)))
@@ -988,7 +1051,11 @@ def f32_to_bf16(x, stream=None):
 
 
 def bf16_to_f32(x, stream=None):
+    """Device int16 tensor of bf16 bit patterns -> fp32 tensor.  x: int16 of any shape; a view that is not contiguous is
+    copied first."""
     _require_gpu(x)
+    if x.dtype != torch.int16:
+        raise ValueError(f"x must be an int16 tensor of bf16 bits, not {x.dtype}")
     x = x.contiguous()
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     capi.check(capi.lib().mispmm_bf16_to_f32(_stream_ptr(stream), x.numel(), _p(x), _p(out)))
@@ -996,25 +1063,29 @@ def bf16_to_f32(x, stream=None):
 
 
 def spmm_bsr_bf16(a, blocks_bf16, b_bf16, out_bf16=False, out=None, stream=None):
-    """a: DeviceBSR (index arrays used), blocks_bf16 / b_bf16: int16 tensors of bf16 bits."""
-    _require_gpu(blocks_bf16, b_bf16)
-    n = b_bf16.shape[1]
-    if out is None:
-        out = torch.empty((a.num_rows, n), dtype=torch.int16 if out_bf16 else torch.float32, device=b_bf16.device)
+    """C = A @ B on MFMA (mispmm_bsr_bf16).  a: DeviceBSR [M x K] (index arrays used); blocks_bf16: A's blocks as a contiguous
+    int16 tensor of bf16 bits, num_blocks * bS * bS elements in A's block order; b_bf16: [K, N] int16 tensor of bf16 bits, unit
+    column stride, any row stride of at least N.  Returns [M, N] float32, or int16 bf16 bits with out_bf16; out= takes the
+    result where given: that shape and dtype, unit column stride, any row stride of at least N."""
+    _require_gpu(a.block_row_ptrs, blocks_bf16, b_bf16, out)
+    _flat(blocks_bf16, "blocks_bf16", torch.int16, a.num_blocks * a.block_row_size * a.block_col_size)
+    n, ldb, out, ldc = _bf16_b_and_out(b_bf16, out_bf16, out, a.num_rows, a.num_cols)
     capi.check(capi.lib().mispmm_bsr_bf16(_stream_ptr(stream), a.num_rows // a.block_row_size, a.num_cols,
                                           a.block_row_size, a.block_col_size, a.num_blocks, _p(a.block_row_ptrs),
-                                          _p(a.block_col_idxs), _p(blocks_bf16), _p(b_bf16), n, b_bf16.stride(0),
-                                          _p(out), out.stride(0), int(bool(out_bf16))))
+                                          _p(a.block_col_idxs), _p(blocks_bf16), _p(b_bf16), n, ldb, _p(out), ldc, int(bool(out_bf16))))
     return out
 
 
 def _bf16_ld(t, what):
-    if t.dim() != 2 or t.dtype != torch.int16 or t.stride(1) != 1 and t.shape[1] > 1:
-        raise ValueError(f"{what} must be a 2-D int16 tensor of bf16 bits with unit column stride")
-    ld = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
-    if ld < t.shape[1]:
-        raise ValueError(f"{what} must not overlap its own rows (row stride {ld} < {t.shape[1]} columns), e.g. an expanded tensor")
-    return ld
+    return _dense(t, what, torch.int16)
+
+
+def _bf16_b_and_out(b_bf16, out_bf16, out, num_rows, num_cols):
+    """(N, ldb, C, ldc) of C = A @ B with B in bf16 bits for an A of num_rows x num_cols; C float32, or int16 with out_bf16."""
+    ldb = _dense(b_bf16, "b_bf16", torch.int16, num_cols)
+    n = b_bf16.shape[1]
+    c, ldc = _dense_out(out, num_rows, n, b_bf16, torch.int16 if out_bf16 else torch.float32)
+    return n, ldb, c, ldc
 
 
 def sddmm_bsr_bf16(a, x_bf16, y_bf16, out_bf16=False, out=None, stream=None):
@@ -1028,7 +1099,7 @@ def sddmm_bsr_bf16(a, x_bf16, y_bf16, out_bf16=False, out=None, stream=None):
     if a.block_col_size != bs:
         raise ValueError(f"blocks must be square, not {bs} x {a.block_col_size}")
     if x_bf16.shape[0] != a.num_rows or y_bf16.shape[0] != a.num_cols or x_bf16.shape[1] != y_bf16.shape[1]:
-        raise ValueError(f"A is {a.num_rows} x {a.num_cols}: x must be [{a.num_rows}, N] and y [{a.num_cols}, N], not "
+        raise ValueError(f"A is {a.num_rows} x {a.num_cols}: x_bf16 must be [{a.num_rows}, N] and y_bf16 [{a.num_cols}, N], not "
                          f"{tuple(x_bf16.shape)} and {tuple(y_bf16.shape)}")
     dtype = torch.int16 if out_bf16 else torch.float32
     if out is None:
@@ -1298,13 +1369,13 @@ class DeviceBSRC:
 
 
 def spmm_bsrc_bf16(a, b_bf16, out_bf16=False, out=None, stream=None):
-    """a: DeviceBSRC, b_bf16: int16 tensor of bf16 bits [K, N]; fp32 (or bf16) C."""
-    _require_gpu(a.step_ptrs, b_bf16)
-    n = b_bf16.shape[1]
-    if out is None:
-        out = torch.empty((a.num_rows, n), dtype=torch.int16 if out_bf16 else torch.float32, device=b_bf16.device)
+    """a: DeviceBSRC [M x K]; b_bf16: [K, N] int16 tensor of bf16 bits, unit column stride, any row stride of at least N.
+    Returns [M, N] float32, or int16 bf16 bits with out_bf16; out= takes the result where given: that shape and dtype, unit
+    column stride, any row stride of at least N."""
+    _require_gpu(a.step_ptrs, b_bf16, out)
+    n, ldb, out, ldc = _bf16_b_and_out(b_bf16, out_bf16, out, a.num_rows, a.num_cols)
     capi.check(capi.lib().mispmm_bsrc_bf16(_stream_ptr(stream), a.num_rows // 16, a.num_cols, a.num_steps, _p(a.step_ptrs),
-                                           _p(a.cols), _p(a.tiles), _p(b_bf16), n, b_bf16.stride(0), _p(out), out.stride(0),
+                                           _p(a.cols), _p(a.tiles), _p(b_bf16), n, ldb, _p(out), ldc,
                                            int(bool(out_bf16))))
     return out
 
@@ -1346,19 +1417,20 @@ class DeviceBSRCSlots:
 
 
 def spmm_bsrc_slots_bf16(a, b_bf16, out_bf16=False, out=None, stream=None):
-    """a: DeviceBSRCSlots, b_bf16: int16 tensor of bf16 bits [K, N]; fp32 (or bf16) C."""
-    _require_gpu(a.extra_ptrs, b_bf16)
-    n = b_bf16.shape[1]
-    if out is None:
-        out = torch.empty((a.num_rows, n), dtype=torch.int16 if out_bf16 else torch.float32, device=b_bf16.device)
+    """a: DeviceBSRCSlots [M x K]; b_bf16, out_bf16 and out as spmm_bsrc_bf16 takes them."""
+    _require_gpu(a.extra_ptrs, b_bf16, out)
+    n, ldb, out, ldc = _bf16_b_and_out(b_bf16, out_bf16, out, a.num_rows, a.num_cols)
     capi.check(capi.lib().mispmm_bsrc_slots_bf16(_stream_ptr(stream), a.num_rows // 16, a.num_cols, a.num_steps, _p(a.extra_ptrs),
-                                                 _p(a.cols), _p(a.tiles), _p(b_bf16), n, b_bf16.stride(0), _p(out), out.stride(0),
+                                                 _p(a.cols), _p(a.tiles), _p(b_bf16), n, ldb, _p(out), ldc,
                                                  int(bool(out_bf16))))
     return out
 
 
 def dense_transpose(x, stream=None):
+    """x^T of a 2-D float32 device tensor (mispmm_dense_transpose_f32); a view that is not contiguous is copied first."""
     _require_gpu(x)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"x must be a 2-D float32 tensor, not {x.dtype} {tuple(x.shape)}")
     x = x.contiguous()
     out = torch.empty((x.shape[1], x.shape[0]), dtype=torch.float32, device=x.device)
     capi.check(capi.lib().mispmm_dense_transpose_f32(_stream_ptr(stream), x.shape[0], x.shape[1], _p(x), _p(out)))
@@ -1434,22 +1506,10 @@ def _spmm_rows_bf16(what, num_rows, num_cols, nnz, row_ptrs, row_nnz, col_idxs, 
     _require_gpu(col_idxs, data, b_bf16, out)
     if data.dtype != torch.float32:
         raise ValueError(f"{what} takes a float32 matrix, not {data.dtype}")
-    if acc not in capi.ACC_MODES:
-        raise ValueError(f"acc must be one of {sorted(capi.ACC_MODES)}, not {acc!r}")
-    ldb = _bf16_ld(b_bf16, "b_bf16")
-    if b_bf16.shape[0] != num_cols:
-        raise ValueError(f"B has {b_bf16.shape[0]} rows, A has {num_cols} columns")
-    n = b_bf16.shape[1]
-    dtype = torch.int16 if out_bf16 else torch.float32
-    if out is None:
-        out = torch.empty((num_rows, n), dtype=dtype, device=b_bf16.device)
-    if out.dim() != 2 or out.dtype != dtype or tuple(out.shape) != (num_rows, n) or out.stride(1) != 1 and n > 1:
-        raise ValueError(f"out must be a 2-D {dtype} tensor of shape {(num_rows, n)} with unit column stride")
-    ldc = out.stride(0) if num_rows > 1 else max(n, out.stride(0))
-    if ldc < n:
-        raise ValueError(f"out must not overlap its own rows (row stride {ldc} < {n} columns)")
+    mode = _acc_mode(acc)
+    n, ldb, out, ldc = _bf16_b_and_out(b_bf16, out_bf16, out, num_rows, num_cols)
     capi_bf16.check(capi_bf16.lib().mispmm_rows_bf16(_stream_ptr(stream), num_rows, num_cols, nnz, _p(row_ptrs), int(row_nnz), _p(col_idxs),
-                                                     _p(data), _p(b_bf16), n, ldb, _p(out), ldc, int(bool(out_bf16)), capi.ACC_MODES[acc],
+                                                     _p(data), _p(b_bf16), n, ldb, _p(out), ldc, int(bool(out_bf16)), mode,
                                                      int(bool(sum_f32))))
     return out
 
@@ -1476,6 +1536,9 @@ def spmm_coo_bf16(a, b_bf16, out_bf16=False, out=None, acc="reference", stream=N
     if a.data.dtype != torch.float32:
         raise ValueError(f"spmm_coo_bf16 takes a float32 matrix, not {a.data.dtype}")
     if a.row_bounds is None:
+        _require_gpu(b_bf16, out)            # the first product launches twice: refuse a bad operand before the first launch
+        _acc_mode(acc)
+        out = _bf16_b_and_out(b_bf16, out_bf16, out, a.num_rows, a.num_cols)[2]
         a.row_bounds = coo_row_bounds(a, stream)
     return _spmm_rows_bf16("spmm_coo_bf16", a.num_rows, a.num_cols, a.nnz, a.row_bounds, 0, a.col_idxs, a.data, b_bf16, out_bf16, out, acc, True,
                            stream)
