@@ -33,9 +33,12 @@ Both gradients come back in bfloat16.  The CSR product with fp32 values and the 
     out = sparse_attention(a, q, k, v, fused=True)     # float32: one launch for all heads (ops.attention_csr), [H, ...] operands
     out = sparse_attention(a, q, k, v, fused=True, fused_backward=True)   # ... and the backward in at most two (ops.attention_csr_bwd)
 
-Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, bf16 operands for the fused CSR attention and a
-gradient for its bias, the column-compacted block layouts (their tiles are built on the host from the values), a device kernel for
-the blocks[perm] transpose."""
+    out = sparse_attention_bf16(a, q, k, v)            # bfloat16 q, k, v: one launch (attn_csr_bf16.attention_csr_bf16); the
+                                                       # backward is ops.attention_csr_bwd on the widened operands
+
+Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, a fused CSR attention backward that reads bf16 itself,
+a gradient for the fused CSR attention's bias, the column-compacted block layouts (their tiles are built on the host from the
+values), a device kernel for the blocks[perm] transpose."""
 import dataclasses
 from dataclasses import dataclass
 
@@ -653,3 +656,73 @@ def spmm_bf16(a, values, b, out_dtype=torch.bfloat16, acc="fast"):
     if acc not in ("reference", "fast"):
         raise ValueError(f"acc must be 'reference' or 'fast', not {acc!r}")
     return _SpmmCsrBf16.apply(values, b, a, out_bf16, acc)
+
+
+# ---- fused attention on a CSR pattern with the activations in bf16 (attn_csr_bf16.attention_csr_bf16)
+class _SparseAttentionBf16(torch.autograd.Function):
+    """The forward in one launch for all heads, reading bf16 (fp32 out and lse); q, k, v, out and lse are saved.  The backward
+    is ops.attention_csr_bwd on the widened q, k, v with the saved fp32 out and lse, every gradient rounded once."""
+    @staticmethod
+    def forward(ctx, q, k, v, a, scale, bias, out_bf16):
+        from . import attn_csr_bf16
+        q, k, v = q.detach(), k.detach(), v.detach()
+        out, lse = attn_csr_bf16.attention_csr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, bias=bias, return_lse=True)
+        ctx.a, ctx.scale, ctx.bias = a, scale, bias
+        ctx.save_for_backward(q, k, v, out, lse)
+        return ops.f32_to_bf16(out).view(torch.bfloat16) if out_bf16 else out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        a, needs = ctx.a, ctx.needs_input_grad
+        if not any(needs[:3]):
+            return (None,) * 7
+        q, k, v, out, lse = ctx.saved_tensors
+        if grad_out.dtype == torch.bfloat16:
+            grad_out = ops.bf16_to_f32(_bits(grad_out))            # exact; a view that is not contiguous is copied there
+        elif grad_out.stride(-1) != 1 or grad_out.stride(-2) < grad_out.shape[-1] or (grad_out.dim() == 3 and grad_out.stride(0) < 1):
+            grad_out = grad_out.contiguous()                       # e.g. out.sum().backward() hands in an expanded scalar
+        qf, kf, vf = (ops.bf16_to_f32(_bits(t)) for t in (q, k, v))
+        grads = ops.attention_csr_bwd(a.fwd, a.tpattern, a.perm32(), qf, kf, vf, out, lse, grad_out, scale=ctx.scale, bias=ctx.bias,
+                                      need=tuple(needs[:3]))
+        return (*(None if g is None else ops.f32_to_bf16(g).view(torch.bfloat16) for g in grads), None, None, None, None)
+
+
+def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfloat16):
+    """Attention on A's pattern with the activations in bfloat16: row r attends to the columns A stores in row r, one launch
+    for all heads (attn_csr_bf16.attention_csr_bf16: fp32 arithmetic on the exactly widened operands, online softmax, neither
+    scores nor weights written, no fp32 copy of q, k or v).
+    a: a float32 TrainableCSR [M x K] (its values are not read); q: [M, D], k: [K, D], v: [K, Dv] torch.bfloat16 device
+    tensors, or [H, ...] with any head and row strides and unit column stride; D and Dv from 1 to 256.  scale defaults to
+    D ** -0.5.  bias: a float32 tensor over A's entries, [nnz] or [H, nnz], added to the scaled scores, -Inf = a masked entry;
+    a constant: one that requires a gradient is refused.  out_dtype: torch.bfloat16 (the default) or torch.float32.  The
+    kernel is always asked for its fp32 out and lse, which the backward reads; a bfloat16 result is ops.f32_to_bf16 of that
+    out -- ONE extra elementwise launch, the same single rounding to nearest even the kernel's own bf16 store makes.
+    Differentiable in q, k and v.  The backward is DEFINED as ops.attention_csr_bwd (at most two launches for all heads) on
+    ops.bf16_to_f32 of q, k and v with the saved fp32 out and lse; grad_out is widened exactly where it is bfloat16 and used as
+    it is where float32; work for inputs that need no gradient is skipped; every gradient is rounded once by ops.f32_to_bf16
+    and comes back in bfloat16.  Not built: a fused backward that reads bf16 itself (the three widenings and their fp32 copies
+    are the cost of this one)."""
+    ops._require_gpu(a.fwd.row_ptrs, q, k, v, bias)
+    out_bf16 = _check_out_dtype(out_dtype)
+    if a.fwd.data.dtype != torch.float32:
+        raise ValueError("sparse_attention_bf16 takes a float32 matrix")
+    dims = {t.dim() for t in (q, k, v)}
+    if dims not in ({2}, {3}):
+        raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    for t, rows, what in ((q, a.fwd.num_rows, "q"), (k, a.fwd.num_cols, "k"), (v, a.fwd.num_cols, "v")):
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"{what} must be torch.bfloat16, not {t.dtype}")
+        if t.shape[-2] != rows or t.shape[:-2] != q.shape[:-2]:
+            raise ValueError(f"{what} must be [{rows}, N] or [H, {rows}, N] with q's H, not {tuple(t.shape)}")
+    if q.shape[-1] != k.shape[-1]:
+        raise ValueError(f"q and k must have the same number of columns, not {q.shape[-1]} and {k.shape[-1]}")
+    if bias is not None:
+        if bias.requires_grad:
+            raise ValueError("bias is a constant: it gets no gradient and must not require one")
+        if bias.dtype != torch.float32:
+            raise ValueError(f"bias must be torch.float32, not {bias.dtype}")
+        bias = bias.detach()
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    return _SparseAttentionBf16.apply(q, k, v, a, float(scale), bias, out_bf16)
