@@ -688,7 +688,35 @@ class _SparseAttentionBf16(torch.autograd.Function):
         return (*(None if g is None else ops.f32_to_bf16(g).view(torch.bfloat16) for g in grads), None, None, None, None)
 
 
-def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfloat16):
+class _SparseAttentionBf16FusedBwd(torch.autograd.Function):
+    """The same forward with a bfloat16 result; the backward is ONE attn_csr_bf16.attention_csr_bf16_bwd call on the saved q, k,
+    v, fp32 out and lse and the bfloat16 grad_out: at most two launches for all heads, nothing widened or narrowed through
+    memory, `need` set from the inputs that require a gradient."""
+    @staticmethod
+    def forward(ctx, q, k, v, a, scale, bias):
+        from . import attn_csr_bf16
+        q, k, v = q.detach(), k.detach(), v.detach()
+        out, lse = attn_csr_bf16.attention_csr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, bias=bias, return_lse=True)
+        ctx.a, ctx.scale, ctx.bias = a, scale, bias
+        ctx.save_for_backward(q, k, v, out, lse)
+        return ops.f32_to_bf16(out).view(torch.bfloat16)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        from . import attn_csr_bf16
+        a, needs = ctx.a, ctx.needs_input_grad
+        if not any(needs[:3]):
+            return (None,) * 6
+        q, k, v, out, lse = ctx.saved_tensors
+        if grad_out.stride(-1) != 1 or grad_out.stride(-2) < grad_out.shape[-1] or (grad_out.dim() == 3 and grad_out.stride(0) < 1):
+            grad_out = grad_out.contiguous()                       # e.g. out.sum().backward() hands in an expanded scalar
+        grads = attn_csr_bf16.attention_csr_bf16_bwd(a.fwd, a.tpattern, a.perm32(), _bits(q), _bits(k), _bits(v), out, lse, _bits(grad_out),
+                                                     scale=ctx.scale, bias=ctx.bias, need=tuple(needs[:3]), grads_bf16=True)
+        return (*(None if g is None else g.view(torch.bfloat16) for g in grads), None, None, None)
+
+
+def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfloat16, fused_backward=False):
     """Attention on A's pattern with the activations in bfloat16: row r attends to the columns A stores in row r, one launch
     for all heads (attn_csr_bf16.attention_csr_bf16: fp32 arithmetic on the exactly widened operands, online softmax, neither
     scores nor weights written, no fp32 copy of q, k or v).
@@ -701,8 +729,16 @@ def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfl
     Differentiable in q, k and v.  The backward is DEFINED as ops.attention_csr_bwd (at most two launches for all heads) on
     ops.bf16_to_f32 of q, k and v with the saved fp32 out and lse; grad_out is widened exactly where it is bfloat16 and used as
     it is where float32; work for inputs that need no gradient is skipped; every gradient is rounded once by ops.f32_to_bf16
-    and comes back in bfloat16.  Not built: a fused backward that reads bf16 itself (the three widenings and their fp32 copies
-    are the cost of this one)."""
+    and comes back in bfloat16 (the three widenings and their fp32 copies are the cost of this one).
+    fused_backward=True (needs out_dtype=torch.bfloat16; off by default): the backward is ONE
+    attn_csr_bf16.attention_csr_bf16_bwd call on the saved q, k, v, fp32 out and lse and the bfloat16 grad_out -- at most two
+    launches for all heads that read bf16 themselves and round each gradient once at the store; a grad_out that is not
+    unit-stride with rows that do not overlap is made contiguous first.  On 16-byte lanes its gradients are not the default
+    backward's bits (a lane's dot-product chain covers 8 columns against 4) and are held to the same derived tolerances.
+    Not built: a fused backward for a float32 grad_out, which is why the keyword is refused with out_dtype=torch.float32."""
+    if fused_backward and out_dtype == torch.float32:
+        raise ValueError("fused_backward=True needs out_dtype=torch.bfloat16: with a float32 out, grad_out would be float32, and the fused "
+                         "bf16 backward reads a bfloat16 grad_out")
     ops._require_gpu(a.fwd.row_ptrs, q, k, v, bias)
     out_bf16 = _check_out_dtype(out_dtype)
     if a.fwd.data.dtype != torch.float32:
@@ -725,4 +761,6 @@ def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfl
         bias = bias.detach()
     if scale is None:
         scale = q.shape[-1] ** -0.5
+    if fused_backward:
+        return _SparseAttentionBf16FusedBwd.apply(q, k, v, a, float(scale), bias)
     return _SparseAttentionBf16.apply(q, k, v, a, float(scale), bias, out_bf16)
