@@ -1,5 +1,6 @@
-// The lane group of the fused fp32 attention on a CSR pattern, written once for the three kernels that are built on it:
-// attn_csr_kernel (attn_csr.hip) and the row pass and the column pass of the backward (bwd/attn_csr_bwd.hip).
+// The lane group of the fused attention on a CSR pattern, written once for the three kernels that are built on it: the forward
+// (attn_csr_fwd.hpp) and the row pass and the column pass of the backward (attn_csr_bwd.hpp), each written once over the element
+// policy of elem.hpp and instantiated for fp32 and for bf16 operands by the four libraries' own units.
 //
 // Shape: G lanes own one (head, row) of the pass's own pattern; a lane owns VEC consecutive columns of each of NCH column chunks
 // of G * VEC and holds its slices of the row's operands and of the fp32 accumulators in registers (G and NCH from max(D, Dv):
@@ -18,12 +19,14 @@
 // What is NOT here, and stands in each kernel as before:
 //  - the fetch of a batch's keys one batch ahead: where it stands relative to the batch's own reads is what makes it work, and
 //    each kernel's loop spells it out;
-//  - the item decode with its two early returns, the broadcast-and-fma accumulate, the masked row store and the forward's dot
-//    chain.  Each was tried as a helper that takes the kernel's arrays by reference, and each changed the ISA of some of the 30
+//  - the item decode with its two early returns, the broadcast-and-fma accumulate, the masked row store and the dot chains.
+//    Each was tried as a helper that takes the kernel's arrays by reference, and each changed the ISA of some of the
 //    instances (registers, schedule of the row's first reads): the helper is optimised on its own before it is inlined, and the
-//    scheduler sees another order.  Helpers that take and return VALUES (join_off, lane_off, dot_chain) and helpers that wrap the
-//    very lambda the kernel had (gather_rows) left every instance as it was.
-// The header lies beside its users and not in csrc/: every csrc/*.hpp is a prerequisite of libmispmm.so, and the census
+//    scheduler sees another order.  Helpers that take and return VALUES (join_off, the policy's lane_off, load and at) and
+//    helpers that wrap the very lambda the kernel had (the policy's gather) left every instance as it was (DESIGN.md section 9
+//    items 17, 18 and 22).
+// What depends on the element type (a lane's offset, the gather, the list of instances) is in elem.hpp.
+// The headers lie beside their users and not in csrc/: every csrc/*.hpp is a prerequisite of libmispmm.so, and the census
 // tests read csrc/ for its kernel tags.  The host pieces have internal linkage: each library exports its one entry point.
 #pragma once
 #include "lane_moves.hpp"
@@ -66,49 +69,8 @@ __device__ __forceinline__ float transpose_sum(const float *acc, uint32_t lane) 
     return s;
 }
 
-// byte offset of the lane's columns of chunk c in a row of `width` columns; past the width: the dropped-load mark
-template <int G, int VEC>
-__device__ __forceinline__ uint32_t lane_off(uint32_t lane, int c, uint32_t width) {
-    const uint32_t col = c * (G * VEC) + lane * VEC;
-    return col < width ? col * 4u : kDropLoad;
-}
-
-// the lane's slices of the batch's 8 rows of one operand; key: byte offset of the row of entry `sub`, or the mark
-template <int VEC, int NCH>
-__device__ __forceinline__ void gather_rows(uint32_t key, rsrc_t r, const uint32_t (&off)[NCH], typename VecOf<VEC>::type (&rows)[kLgBatch][NCH]) {
-    static_for<0, kLgBatch>([&](auto j_tag) {
-        constexpr int j = decltype(j_tag)::value;
-        const uint32_t kj = group_bcast<8, j>(key);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) rows[j][c] = buffer_load_vec<VEC>(r, join_off(kj, off[c]), 0);
-    });
-}
-
-// acc + the lane's part of <a, b> over one chunk: one fma chain in column order.  The backward's four chains; in the forward it
-// moves the Q[r] read of the VEC == 4 instances behind the first key fetch, so the chain is spelled out there
-template <int VEC>
-__device__ __forceinline__ float dot_chain(typename VecOf<VEC>::type a, typename VecOf<VEC>::type b, float acc) {
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) acc = __builtin_fmaf(vec_get<VEC>(a, v), vec_get<VEC>(b, v), acc);
-    return acc;
-}
-
 // elements one head's rows span: the last row ends with its last column, not with its stride
 uint64_t span(uint64_t rows, uint32_t ld, uint32_t width) { return rows == 0 ? 0 : (rows - 1) * ld + width; }
-
-// f(G, VEC, NCH) as constants -- lanes of a row, elements of a lane, chunks of G * VEC columns: the one list of the instances
-// that exist
-template <class F>
-void with_instance(int vec, int g, uint32_t width, F &&f) {
-    using std::integral_constant;
-    if (vec == 4) {
-        with_group(g, [&](auto gr) { f(gr, integral_constant<int, 4>{}, integral_constant<int, 1>{}); });  // 64 x 4 covers 256
-    } else if (!try_const<8, 16, 32>(g, [&](auto gr) { f(gr, integral_constant<int, 1>{}, integral_constant<int, 1>{}); })) {
-        const uint32_t chunks = ceil_div(width, static_cast<uint32_t>(kWave));
-        with_const<1, 2, 4>(chunks <= 1 ? 1 : chunks == 2 ? 2 : 4,
-                            [&](auto ch) { f(integral_constant<int, 64>{}, integral_constant<int, 1>{}, ch); });
-    }
-}
 
 // the grid of a pass over `rows` rows of each of H heads, a group of G lanes per row: completes p, returns the blocks to launch
 template <int G, class Params>

@@ -19,7 +19,7 @@ from _softmax_ref import matrix
 from test_census_cpu import _symbol_tool
 
 NAME = "mispmm_attn_csr_bf16_bwd"
-INSTANCES = {"attn_csr_bf16_bwd_row_kernel": 9, "attn_csr_bf16_bwd_col_kernel": 9}
+INSTANCES = {"attn_csr_bwd_row_kernel": 9, "attn_csr_bwd_col_kernel": 9}
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -165,8 +165,10 @@ def test_the_library_holds_nine_instances_per_pass_and_the_tag_table_lists_each(
     assert found == INSTANCES, f"kernel templates: instances in the library {found}, recorded here {INSTANCES}"
     tags = set()
     for kind in ("row", "col"):
-        for args in set(re.findall(rf"__device_stub__attn_csr_bf16_bwd_{kind}_kernel<([^>]*)>", out)):
-            g, vec, nch = (int(s.strip()) for s in args.split(","))
+        for args in set(re.findall(rf"__device_stub__attn_csr_bwd_{kind}_kernel<([^>]*)>", out)):
+            elem, *consts = (s.strip() for s in args.split(","))          # the element policy, then G, VEC, NCH
+            assert elem.endswith("::ElemBf16"), args
+            g, vec, nch = (int(s) for s in consts)
             tags.add(f"attn_csr_bf16_bwd_{kind}<G{g},V{vec},C{nch}>")
     assert tags == set(bb.TAGS), (sorted(tags - set(bb.TAGS)), sorted(set(bb.TAGS) - tags))
     assert len(bb.TAGS) == sum(INSTANCES.values()) == 18

@@ -18,7 +18,7 @@ from _softmax_ref import matrix
 from test_census_cpu import _symbol_tool
 
 NAME = "mispmm_attn_csr_bf16"
-INSTANCES = {"attn_csr_bf16_kernel": 9}       # __device_stub__ symbols of libmispmm_attn_csr_bf16.so per kernel template
+INSTANCES = {"attn_csr_kernel": 9}       # __device_stub__ symbols of libmispmm_attn_csr_bf16.so per kernel template
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -123,11 +123,13 @@ def test_the_library_holds_nine_instances_of_one_template_and_the_tag_table_list
         found[name] = found.get(name, 0) + 1
     assert found == INSTANCES, f"kernel template: instances in the library {found}, recorded here {INSTANCES}"
     tags = set()
-    for args in set(re.findall(r"__device_stub__attn_csr_bf16_kernel<([^>]*)>", out)):
-        g, vec, nch = (int(s.strip()) for s in args.split(","))
+    for args in set(re.findall(r"__device_stub__attn_csr_kernel<([^>]*)>", out)):
+        elem, *consts = (s.strip() for s in args.split(","))          # the element policy, then G, VEC, NCH
+        assert elem.endswith("::ElemBf16"), args
+        g, vec, nch = (int(s) for s in consts)
         tags.add(f"attn_csr_bf16<G{g},V{vec},C{nch}>")
     assert tags == set(bref.TAGS), (sorted(tags - set(bref.TAGS)), sorted(set(bref.TAGS) - tags))
-    assert len(bref.TAGS) == INSTANCES["attn_csr_bf16_kernel"] == 3 + 6
+    assert len(bref.TAGS) == INSTANCES["attn_csr_kernel"] == 3 + 6
     for tag, (d, dv, aligned) in bref.TAGS.items():
         assert bref.tag_of(d, dv, aligned) == tag
         # the smallest shape: one step less in either width is refused or lands on another tag

@@ -104,7 +104,9 @@ def test_the_library_holds_the_recorded_instances_and_the_tag_table_lists_each()
     assert found == INSTANCES, f"kernel template: instances in the library {found}, recorded here {INSTANCES}"
     tags = set()
     for args in set(re.findall(r"__device_stub__attn_csr_kernel<([^>]*)>", out)):
-        g, vec, nch = (int(s.strip()) for s in args.split(","))
+        elem, *consts = (s.strip() for s in args.split(","))          # the element policy, then G, VEC, NCH
+        assert elem.endswith("::ElemF32"), args
+        g, vec, nch = (int(s) for s in consts)
         tags.add(f"attn_csr<f32,G{g},V{vec},C{nch}>")
     assert tags == set(ref.TAGS), (sorted(tags - set(ref.TAGS)), sorted(set(ref.TAGS) - tags))
     assert len(ref.TAGS) == INSTANCES["attn_csr_kernel"]
