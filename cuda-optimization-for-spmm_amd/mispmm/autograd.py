@@ -611,8 +611,8 @@ def _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16, fused_backw
 # ---- the CSR product with B in bf16 (ops.spmm_csr_bf16): fp32 values, bf16 activations
 class _SpmmCsrBf16(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, values, b, a, out_bf16, acc):
-        ctx.a, ctx.acc = a, acc
+    def forward(ctx, values, b, a, out_bf16, acc, sddmm):
+        ctx.a, ctx.acc, ctx.sddmm = a, acc, sddmm
         ctx.save_for_backward(values, b)
         c = ops.spmm_csr_bf16(dataclasses.replace(a.fwd, data=values.detach().contiguous()), _bits(b.detach()), out_bf16=out_bf16, acc=acc)
         return c.view(torch.bfloat16) if out_bf16 else c
@@ -626,21 +626,28 @@ class _SpmmCsrBf16(torch.autograd.Function):
         g = ops.f32_to_bf16(grad_c) if grad_c.dtype == torch.float32 else _bits(grad_c)
         grad_values = grad_b = None
         if ctx.needs_input_grad[0]:
-            grad_values = ops.sddmm_csr(a.fwd, ops.bf16_to_f32(g), ops.bf16_to_f32(_bits(b)), acc=ctx.acc)
+            if ctx.sddmm == "bf16":
+                from . import sddmm_bf16
+                grad_values = sddmm_bf16.sddmm_csr_bf16(a.fwd, g, _bits(b), acc=ctx.acc)
+            else:
+                grad_values = ops.sddmm_csr(a.fwd, ops.bf16_to_f32(g), ops.bf16_to_f32(_bits(b)), acc=ctx.acc)
         if ctx.needs_input_grad[1]:
             t = dataclasses.replace(a.tpattern, data=values.detach()[a.perm])
             grad_b = ops.spmm_csr_bf16(t, g, out_bf16=True, acc=ctx.acc).view(torch.bfloat16)
-        return grad_values, grad_b, None, None, None
+        return grad_values, grad_b, None, None, None, None
 
 
-def spmm_bf16(a, values, b, out_dtype=torch.bfloat16, acc="fast"):
+def spmm_bf16(a, values, b, out_dtype=torch.bfloat16, acc="fast", sddmm="f32"):
     """C = A @ B with the activations in bfloat16, differentiable in `values` (float32, A's entries in storage order) and in
     `b` ([K, N] bfloat16, unit column stride, any row stride).  a: a float32 TrainableCSR; out_dtype: torch.bfloat16 or
     torch.float32.  The forward is ops.spmm_csr_bf16, bit for bit (acc="reference": the CSR rule, a double sum).  The
     backward makes grad_C contiguous and, where C is float32, rounds it to bfloat16 (to nearest even) once, as spmm_bsr does.
-    grad_b is the same kernel on A^T's pattern with values[a.perm] and comes back in bfloat16; grad_values is ops.sddmm_csr
-    on grad_C and b widened to float32 (exact), in float32.  A gradient is computed only for the inputs that require one.
-    Not built: an SDDMM on a CSR pattern that reads bf16 itself."""
+    grad_b is the same kernel on A^T's pattern with values[a.perm] and comes back in bfloat16; grad_values is float32 and
+    comes by the path `sddmm` names.  "f32" (the default): ops.sddmm_csr on grad_C and b widened to float32 (exact) by two
+    ops.bf16_to_f32 launches.  "bf16": sddmm_bf16.sddmm_csr_bf16 on the bf16 grad_C and b themselves, one launch and no
+    float32 copy of either; with acc="reference" it has the default path's bits wherever the exact sums fit 53 bits, with
+    acc="fast" the order of its additions is its own on 16-byte lanes (include/mispmm_sddmm_bf16.h).  A gradient is computed
+    only for the inputs that require one."""
     ops._require_gpu(a.fwd.row_ptrs, values, b)
     out_bf16 = _check_out_dtype(out_dtype)
     if a.fwd.data.dtype != torch.float32 or values.dtype != torch.float32:
@@ -655,7 +662,9 @@ def spmm_bf16(a, values, b, out_dtype=torch.bfloat16, acc="fast"):
         raise ValueError("b must have unit column stride")
     if acc not in ("reference", "fast"):
         raise ValueError(f"acc must be 'reference' or 'fast', not {acc!r}")
-    return _SpmmCsrBf16.apply(values, b, a, out_bf16, acc)
+    if sddmm not in ("f32", "bf16"):
+        raise ValueError(f"sddmm must be 'f32' or 'bf16', not {sddmm!r}")
+    return _SpmmCsrBf16.apply(values, b, a, out_bf16, acc, sddmm)
 
 
 # ---- fused attention on a CSR pattern with the activations in bf16 (attn_csr_bf16.attention_csr_bf16)
