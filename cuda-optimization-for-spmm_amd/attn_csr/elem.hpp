@@ -21,18 +21,12 @@
 // the upper half of an fp32 (exact, nothing flushed or quieted); V8 is 8 consecutive columns as one 16-byte buffer load (the
 // register cost of an fp32 V4 slice), V1 one buffer_load_ushort per column.
 #pragma once
+#include "bf16_lanes.hpp"
 #include "lane_group.hpp"
 
 namespace mispmm {
 
 namespace {
-
-using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
-
-// VEC bf16 elements of a row as they are loaded; a single element zero-extended
-template <int VEC> struct RawOf;
-template <> struct RawOf<1> { using type = uint32_t; };
-template <> struct RawOf<8> { using type = u32x4; };
 
 // one rounding to nearest even, a NaN stays a NaN: v_cvt_pk_bf16_f32, as rows_bf16/ and mispmm_f32_to_bf16
 __device__ __forceinline__ uint32_t bf16_bits(float x) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(x)); }
@@ -135,16 +129,10 @@ struct ElemBf16 : ElemCommon<ElemBf16> {
     using row_t = size_t;
 
     template <int VEC>
-    static __device__ __forceinline__ raw_t<VEC> load(rsrc_t r, uint32_t off) {
-        if constexpr (VEC == 1) return __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, 0);
-        else return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-    }
+    static __device__ __forceinline__ raw_t<VEC> load(rsrc_t r, uint32_t off) { return buffer_load_bf16<VEC>(r, off); }
     // element i widened to fp32 exactly: the bits moved to the upper half
     template <int VEC>
-    static __device__ __forceinline__ float at(const raw_t<VEC> &raw, int i) {
-        if constexpr (VEC == 1) return __uint_as_float(raw << 16);
-        else return __uint_as_float((i & 1) ? (raw[i >> 1] & 0xFFFF0000u) : (raw[i >> 1] << 16));
-    }
+    static __device__ __forceinline__ float at(const raw_t<VEC> &raw, int i) { return widen<VEC>(raw, i); }
     template <int VEC>
     static __device__ __forceinline__ float held(const held_t<VEC> &h, int i) { return h[i]; }
     static __device__ __forceinline__ row_t row_of(void *, uint32_t h, uint64_t head, uint32_t row, uint32_t ld) {

@@ -1,25 +1,12 @@
-// SDDMM on a CSR pattern: out[e] = <X[row(e), :], Y[col(e), :]> for every stored entry e of A (A's values are not read).
-// The backward of C = A * B with respect to A's values is this product with X = dC, Y = B.
-//
-// Shape: the row-gather kernel's (row_gather.hpp) -- G lanes own one row of A, a lane owns VEC consecutive columns of each
-// column chunk of G * VEC.  The group keeps its slice of X[row] in registers (up to 4 chunks; wider
-// rows re-read X per batch, from L1), walks the row's entries in batches of 8 with the 8 x NCH Y-row reads of a batch
-// independent of each other, and sums every lane's 8 partial dot products across the group with a TRANSPOSING butterfly:
-// in step k a lane keeps the half of its values whose entry number has bit k equal to its own lane bit k and hands the other
-// half to lane ^ (1 << k), so 8 values cross the group in 4 + 2 + 1 moves (then one per further doubling of G) instead of
-// 8 * log2(G), and lane i of the group ends up with the result of entry i of the batch: lanes 0..7 store 8 consecutive
-// elements of `out`.  The moves (lane_moves.hpp) are DPP (quad_perm, row_ror) or ds_swizzle; lane ^ 32 goes through ds_bpermute.
-// A batch's column keys reach the group by DPP row_newbcast: per key two moves (lane j and lane 8 + j of the 16-lane row) and
-// a select on the lane's own half, 16 moves per batch; with G >= 16 one move would do (both halves hold the same keys).
-// Fixed order throughout: run to run identical.  No LDS, no scratch.
-#include "lane_moves.hpp"
+// SDDMM on a CSR pattern in fp32 and fp64: out[e] = <X[row(e), :], Y[col(e), :]> for every stored entry e of A (A's values are
+// not read).  The backward of C = A * B with respect to A's values is this product with X = dC, Y = B.
+// The kernel body, its shape and the launch ladder are sddmm_csr.hpp's; here: the element policy over T, the four arithmetics,
+// the kernel with its parameter list and its store, the launch and the entry points.
+#include "sddmm_csr.hpp"
 
 namespace mispmm {
 
 namespace {
-
-constexpr int kSdBlock = 256;  // threads per workgroup
-constexpr int kSdBatch = 8;    // entries of a row summed at once: lane i < 8 of a group stores the i-th
 
 template <class T, int VEC> struct SdVec;
 template <> struct SdVec<float, 1> { using type = float; };
@@ -27,17 +14,23 @@ template <> struct SdVec<float, 4> { using type = f32x4; };
 template <> struct SdVec<double, 1> { using type = double; };
 template <> struct SdVec<double, 2> { using type = double __attribute__((ext_vector_type(2))); };
 
-template <class T, int VEC>
-__device__ __forceinline__ typename SdVec<T, VEC>::type sd_load(rsrc_t rsrc, uint32_t voffset) {
-    using vec_t = typename SdVec<T, VEC>::type;
-    if constexpr (sizeof(vec_t) == 4) return __builtin_bit_cast(vec_t, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voffset, 0, 0));
-    else if constexpr (sizeof(vec_t) == 8) return __builtin_bit_cast(vec_t, __builtin_amdgcn_raw_buffer_load_b64(rsrc, voffset, 0, 0));
-    else return __builtin_bit_cast(vec_t, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, 0, 0));
-}
-template <class T, int VEC>
-__device__ __forceinline__ T sd_get(const typename SdVec<T, VEC>::type &v, int i) {
-    if constexpr (VEC == 1) return v; else return v[i];
-}
+// the element policy of sddmm_csr.hpp: a lane's slice is a T or a 16-byte vector of T
+template <class T>
+struct SdElem {
+    using in_t = T;
+    static constexpr uint32_t kBytes = sizeof(T);
+    template <int VEC> using raw_t = typename SdVec<T, VEC>::type;
+    template <int VEC>
+    static __device__ __forceinline__ raw_t<VEC> load(rsrc_t rsrc, uint32_t voffset) {
+        if constexpr (sizeof(raw_t<VEC>) == 4) return __builtin_bit_cast(raw_t<VEC>, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voffset, 0, 0));
+        else if constexpr (sizeof(raw_t<VEC>) == 8) return __builtin_bit_cast(raw_t<VEC>, __builtin_amdgcn_raw_buffer_load_b64(rsrc, voffset, 0, 0));
+        else return __builtin_bit_cast(raw_t<VEC>, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, 0, 0));
+    }
+    template <int VEC>
+    static __device__ __forceinline__ T at(const raw_t<VEC> &v, int i) {
+        if constexpr (VEC == 1) return v; else return v[i];
+    }
+};
 
 // The four arithmetics (mispmm.h, section SDDMM).  T: operand type, A: type of a partial sum.
 struct SdF32Ref {  // the fp32 x fp32 product is exact in fp64, so the fused form rounds exactly where mul + add would: once, at the add
@@ -68,19 +61,13 @@ struct SdF64Fast {
     static __device__ __forceinline__ T finish(A acc) { return acc; }
 };
 
-// one step of the transposing butterfly: 2 * H values in, H out; the lane whose bit MASK is clear keeps the even ones
-template <int MASK, int H, class A>
-__device__ __forceinline__ void fold(const A *in, A *out, bool odd) {
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        const A keep = odd ? in[2 * j + 1] : in[2 * j];
-        const A send = odd ? in[2 * j] : in[2 * j + 1];
-        out[j] = keep + lane_xor<MASK>(send);
-    }
-}
+// the store: entry e of `out`
+template <class T>
+struct SdStore {
+    T *out;
+    __device__ __forceinline__ void operator()(size_t e, T r) const { out[e] = r; }
+};
 
-// NCH > 0: the group's slice of X[row] -- NCH chunks of G * VEC columns -- lives in registers; NCH == 0 (G = 64 only): any N,
-// X re-read chunk by chunk for every batch of entries.
 template <class P, int G, int VEC, int NCH>
 __global__ void __launch_bounds__(kSdBlock) sddmm_csr_kernel(uint32_t M, uint32_t N, uint32_t xcd_chunk, uint32_t ldx, uint32_t ldy,
                                                              const uint32_t *__restrict__ rowPtrs, const uint32_t *__restrict__ colIdxs,
@@ -88,95 +75,7 @@ __global__ void __launch_bounds__(kSdBlock) sddmm_csr_kernel(uint32_t M, uint32_
                                                              const typename P::T *__restrict__ Y, uint32_t y_bytes,
                                                              typename P::T *__restrict__ out) {
     using T = typename P::T;
-    using A = typename P::A;
-    using vec_t = typename SdVec<T, VEC>::type;
-    static_assert(G >= kSdBatch && (G & (G - 1)) == 0 && G <= kWave, "a batch's results sit in the first lanes of a group");
-    static_assert(NCH > 0 || G == kWave, "the chunk loop is for rows wider than a wave");
-    constexpr int GROUPS = kSdBlock / G, E = kSdBatch;
-    constexpr uint32_t ES = sizeof(T), CHUNK = G * VEC;
-    const uint32_t lane = threadIdx.x % G, sub = lane & (E - 1);
-    const uint64_t row64 = static_cast<uint64_t>(xcd_block(blockIdx.x, xcd_chunk)) * GROUPS + threadIdx.x / G;
-    const bool row_ok = row64 < M;
-    const uint32_t row = static_cast<uint32_t>(row64);
-    uint32_t base = 0, len = 0;
-    if (row_ok) {
-        base = rowPtrs[row];
-        len = rowPtrs[row + 1] - base;
-    }
-    if (len == 0) return;  // the lanes a move reads from are all in the lane's own group, which leaves as one
-
-    const rsrc_t xr = make_rsrc(X, x_bytes), yr = make_rsrc(Y, y_bytes);
-    const uint32_t x_row = row * ldx * ES;  // < 2 GiB: the host declines anything larger
-    const uint32_t ldy_bytes = ldy * ES;
-    // byte offset of the lane's columns in chunk c, kDropLoad past N: such a load returns zeros, so a masked lane adds
-    // 0 * 0 = +0 to every live slot (neither the gap columns of a strided operand nor anything behind it is ever read)
-    auto col_off = [&](uint32_t c0) {
-        const uint32_t col = c0 + lane * VEC;
-        return col < N ? col * ES : kDropLoad;
-    };
-    // A Y read's offset is key + column offset and either part may be kDropLoad.  Both at once -- a slot past the row end
-    // in a lane past N -- wrap to offset 0: that lane really reads Y[0][0..VEC).  It is an in-range read that changes no
-    // result: the lane's X is zero, the product (0 * y, a NaN if y is not finite) lands only in the sum of a slot past the
-    // row end, the butterfly keeps the slots apart and the store is guarded.
-    uint32_t off[NCH > 0 ? NCH : 1];
-    vec_t xv[NCH > 0 ? NCH : 1];
-    if constexpr (NCH > 0) {
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            off[c] = col_off(c * CHUNK);
-            xv[c] = sd_load<T, VEC>(xr, x_row + off[c]);
-        }
-    }
-    // entry c0 + sub of the row: every 8-lane segment of the group holds the batch's 8 columns
-    auto fetch = [&](uint32_t c0) {
-        const uint32_t idx = c0 + sub;
-        return colIdxs[static_cast<size_t>(base) + (idx < len ? idx : 0u)];
-    };
-    uint32_t nxt = fetch(0);
-    for (uint32_t s0 = 0; s0 < len; s0 += E) {
-        // a slot past the row end gets key kDropLoad: zeros, and a result nobody stores
-        const uint32_t key = s0 + sub < len ? nxt * ldy_bytes : kDropLoad;
-        nxt = fetch(s0 + E);  // on its way while this batch is gathered
-        A acc[E];
-#pragma unroll
-        for (int j = 0; j < E; ++j) acc[j] = A(0);
-        if constexpr (NCH > 0) {
-            static_for<0, E>([&](auto j_tag) {
-                constexpr int j = decltype(j_tag)::value;
-                const uint32_t kj = group_bcast<8, j>(key);
-                vec_t yv[NCH];
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) yv[c] = sd_load<T, VEC>(yr, kj + off[c]);
-#pragma unroll
-                for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) P::mac(acc[j], sd_get<T, VEC>(xv[c], v), sd_get<T, VEC>(yv[c], v));
-            });
-        } else {
-            uint32_t kj[E];
-            static_for<0, E>([&](auto j_tag) { kj[decltype(j_tag)::value] = group_bcast<8, decltype(j_tag)::value>(key); });
-            for (uint32_t c0 = 0; c0 < N; c0 += CHUNK) {
-                const uint32_t o = col_off(c0);
-                const vec_t x = sd_load<T, VEC>(xr, x_row + o);
-                vec_t yv[E];
-#pragma unroll
-                for (int j = 0; j < E; ++j) yv[j] = sd_load<T, VEC>(yr, kj[j] + o);
-#pragma unroll
-                for (int j = 0; j < E; ++j)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) P::mac(acc[j], sd_get<T, VEC>(x, v), sd_get<T, VEC>(yv[j], v));
-            }
-        }
-        A w[4], u[2], z[1];
-        fold<1, 4>(acc, w, (lane & 1u) != 0);
-        fold<2, 2>(w, u, (lane & 2u) != 0);
-        fold<4, 1>(u, z, (lane & 4u) != 0);
-        A r = z[0];
-        if constexpr (G >= 16) r = r + lane_xor<8>(r);
-        if constexpr (G >= 32) r = r + lane_xor<16>(r);
-        if constexpr (G >= 64) r = r + lane_xor<32>(r);
-        if (lane < E && s0 + lane < len) out[static_cast<size_t>(base) + s0 + lane] = P::finish(r);
-    }
+    sddmm_csr_body<SdElem<T>, P, G, VEC, NCH>(M, N, xcd_chunk, ldx, ldy, rowPtrs, colIdxs, X, x_bytes, Y, y_bytes, SdStore<T>{out});
 }
 
 template <class T>
@@ -199,14 +98,6 @@ void launch_sddmm(const SdArgs<typename P::T> &a) {
     hipLaunchKernelGGL((sddmm_csr_kernel<P, G, VEC, NCH>), dim3(xg.grid), dim3(kSdBlock), 0, a.stream, a.M, a.N, xg.chunk, a.ldx, a.ldy,
                        a.rowPtrs, a.colIdxs, a.X, static_cast<uint32_t>(static_cast<uint64_t>(a.M) * a.ldx * ES), a.Y,
                        static_cast<uint32_t>(static_cast<uint64_t>(a.K) * a.ldy * ES), a.out);
-}
-
-template <class P, int VEC>
-void launch_sddmm_shape(const SdArgs<typename P::T> &a) {
-    if (try_const<8, 16, 32>(pick_group(a.N, VEC), [&](auto g) { launch_sddmm<P, decltype(g)::value, VEC, 1>(a); })) return;
-    // a whole wave per row: 1, 2 or 4 chunks of 64 lanes held in registers, 0 = a loop over any number
-    const uint32_t chunks = ceil_div(a.N, static_cast<uint32_t>(kWave * VEC));
-    with_const<1, 2, 4, 0>(chunks <= 1 ? 1 : chunks == 2 ? 2 : chunks <= 4 ? 4 : 0, [&](auto c) { launch_sddmm<P, 64, VEC, decltype(c)::value>(a); });
 }
 
 template <class PRef, class PFast>
@@ -232,7 +123,11 @@ int sddmm_csr(const char *name, mispmm_stream_t stream, uint32_t M, uint32_t K, 
     const SdArgs<T> a{as_stream(stream), M, K, N, rowPtrs, colIdxs, X, ldx, Y, ldy, out};
     const bool wide = N % WIDE == 0 && ldx % WIDE == 0 && ldy % WIDE == 0 && aligned16(X) && aligned16(Y);
     with_acc<PRef, PFast>(acc_mode, [&](auto acc) {
-        with_const<WIDE, 1>(wide ? WIDE : 1, [&](auto v) { launch_sddmm_shape<typename decltype(acc)::type, decltype(v)::value>(a); });
+        with_const<WIDE, 1>(wide ? WIDE : 1, [&](auto v) {
+            launch_sddmm_shape<decltype(v)::value>(N, [&](auto g, auto c) {
+                launch_sddmm<typename decltype(acc)::type, decltype(g)::value, decltype(v)::value, decltype(c)::value>(a);
+            });
+        });
     });
     MISPMM_LAUNCH_CHECK();
     return MISPMM_OK;
