@@ -4,19 +4,9 @@
 //   z          = fl32(scale * s + mask[e][i][j])                      one fma; no mask: the product (as softmax_bsr.hip)
 //   out_h[r,:] = sum_e sum_j softmax_row(z)[e][j] * V_h[c * bS + j, :Dv]
 //
-// Shape: one WAVE owns 16 matrix rows of one head (a block row at bS = 16, half of one at bS = 32) and walks that block row
-// 32 keys at a step: two blocks at bS = 16 (an odd leftover is a half step: its second tile's scores are -Inf and its V loads
-// are dropped), one block at bS = 32.  Four waves to a workgroup, consecutive units of one head; nothing crosses waves: no
-// LDS, no barrier, no atomics.  Every sum has a fixed order: run to run identical.
-//
-// Both products are computed TRANSPOSED.  Scores: K rows are the A operand and Q rows the B operand (Q's fragments stay in
-// registers for the whole row), so lane (i = l & 15, g = l >> 4) holds the scores of query row i for keys 4g .. 4g + 3 of
-// each of the step's two 16-key tiles.  Second product O^T = V^T * P^T: the B operand is P^T, lane (i, g) supplies
-// P[i][its 8 k slots].  k is only a summation index, so slot 8g + j is NAMED key 4g + j of the first tile and slot 8g + 4 + j
-// key 4g + j of the second: the 8 weights a lane already holds, no lane move.  The A operand is V^T: the lane reads, for the
-// same 8 keys, the TPL consecutive bf16 of V columns TPL * i .. and regroups them per tile with v_perm_b32, exactly as
-// bsr_mfma_bf16 (spmm_bsr.hip) does for its B.  Lane (i, g) then holds O[i][4 TPL g .. 4 TPL g + 4 TPL - 1]: the rescale factor
-// and 1 / l of row i are lane-local and the final store is a run of consecutive elements of out[r].
+// Work unit, lane layout of the two transposed products, loads and the MFMA hazard: attn_bsr_tiles.hpp.  Here the wave's 16
+// rows are matrix rows, a step's 32 rows are keys (a half step's second tile has scores -Inf and its V loads are dropped),
+// X = V and W = P: the rescale factor and 1 / l of row i are lane-local.  Every sum has a fixed order: run to run identical.
 //
 // Online softmax in fp32: a running maximum m (two xor moves over g per step, lane_moves.hpp: the only cross-lane traffic
 // of the loop), running sums and the accumulator O rescaled by exp(mu_old - mu_new) when the maximum moves.  The weights
@@ -29,29 +19,19 @@
 // m is still -Inf (every key so far masked) O and l are exactly 0 and the rescale factor is set to 1: exp(0 - m_new) could
 // overflow and 0 * Inf would poison the row.  Column i of P^T reaches only column i of O^T: a NaN stays in its matrix row.
 //
-// MFMA hazard: O is read by VALU (the rescale) in the iteration after the MFMAs that wrote it, and by the store after the
-// loop -- both over a loop edge, where hipcc does not pad the XDL-write to VALU-read wait (the `store` comment of
-// sddmm_bsr.hip).  settle() spells the wait out once per step for all tiles together: 16 idle cycles, the accumulators
-// passing through the statement so that every read follows it.
+// O is read by VALU (the rescale) in the iteration after the MFMAs that wrote it, and by the store after the loop: settle()
+// once per step, after the step's exponentials and before the rescale, and once before the store.
 //
-// Loads go through buffer descriptors (one per operand and head): a column at or past D / Dv, a block column at or past
-// K / bS and the missing half of a half step become the dropped-load offset: zeros, nothing fetched.  Everything a step
-// reads -- K fragments, the mask's elements, V's rows -- is fetched one step ahead into the other of two register stages (in
-// turn, no copy, as sddmm_bsr.hip has it), and the block columns of a fetch are read one step further ahead by scalar loads:
-// the memory counter is in order, so a step that waited for a load issued inside it would wait for its prefetches too.
-#include "lane_moves.hpp"
+// Everything a step reads -- K fragments, the mask's elements, V's rows -- is fetched one step ahead into the other of two
+// register stages (in turn, no copy, as sddmm_bsr.hip has it), and the block columns of a fetch are read one step further
+// ahead by scalar loads: the memory counter is in order, so a step that waited for a load issued inside it would wait for
+// its prefetches too.
+#include "attn_bsr_tiles.hpp"
 #include "mispmm_attn.h"
 
 namespace mispmm {
 
 namespace {
-
-using bf16x8_t = short __attribute__((ext_vector_type(8)));
-using f32x4_t = float __attribute__((ext_vector_type(4)));
-using u32x2_t = uint32_t __attribute__((ext_vector_type(2)));
-using u32x4_t = uint32_t __attribute__((ext_vector_type(4)));
-
-constexpr int kAttnWaves = 4;
 
 struct AttnParams {
     uint32_t units, wgs_per_head, total, xcd_chunk;  // units: 16-row work units of one head; total: workgroups of all heads
@@ -62,32 +42,23 @@ struct AttnParams {
     uint64_t q_head, k_head, v_head, o_head;         // elements
 };
 
-__device__ __forceinline__ float attn_exp(float t) { return __builtin_amdgcn_exp2f(t * 1.44269504088896340736f); }  // as softmax_bsr.hip
-
-// 8 consecutive bf16 of one row; the 8 columns are inside N or past it together (N is a multiple of 8)
-__device__ __forceinline__ bf16x8_t load_frag(rsrc_t rsrc, uint32_t row_off, uint32_t col, uint32_t N) {
-    const uint32_t off = col < N ? row_off + col * 2u : kDropLoad;
-    return __builtin_bit_cast(bf16x8_t, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
-}
-
 // BS: block size.  DS: 32-column steps of D held (D <= 32 DS).  TPL: accumulator tiles = consecutive V columns per lane
 // (Dv <= 16 TPL).  The arrays are kernel arguments of their own, `const __restrict__`: the block columns then come by scalar
 // loads, which do not queue behind the vector loads in flight.
 template <int BS, int DS, int TPL, bool MASK, bool OUT_BF16>
-__global__ void __launch_bounds__(64 * kAttnWaves)
+__global__ void __launch_bounds__(64 * kTileWaves)
     attn_bsr_kernel(const AttnParams p, const uint32_t *__restrict__ blockRowPtrs, const uint32_t *__restrict__ blockColIdxs,
                     const uint16_t *__restrict__ Q, const uint16_t *__restrict__ K, const uint16_t *__restrict__ V, const float *__restrict__ mask,
                     void *__restrict__ out, float *__restrict__ lse_out) {
-    constexpr uint32_t T = BS / 16;             // work units per block row
-    constexpr uint32_t EPS = BS == 16 ? 2 : 1;  // blocks per 32-key step
+    using W = Walk<BS>;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t item = xcd_block(blockIdx.x, p.xcd_chunk);
     if (item >= p.total) return;
     const uint32_t h = item / p.wgs_per_head;
-    const uint32_t unit = (item - h * p.wgs_per_head) * kAttnWaves + wave;
+    const uint32_t unit = (item - h * p.wgs_per_head) * kTileWaves + wave;
     if (unit >= p.units) return;
-    const uint32_t R = unit / T, sub = unit % T;
+    const uint32_t R = unit / W::T, sub = unit % W::T;
     const uint32_t i = lane & 15, g = lane >> 4;
     const uint32_t row = unit * 16u + i;  // < rows
     const uint32_t bs = blockRowPtrs[R], be = blockRowPtrs[R + 1];
@@ -97,31 +68,12 @@ __global__ void __launch_bounds__(64 * kAttnWaves)
 #pragma unroll
     for (int t = 0; t < TPL; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-    // lane (i, g) holds O[i][TPL (4g + k) + t] in acc[t][k]: for every k a run of TPL consecutive columns, inside Dv or past it
-    // together (Dv is a multiple of 8)
     auto store = [&](float inv, float lse) {
         const size_t base = static_cast<size_t>(h) * p.o_head + static_cast<size_t>(row) * p.ldo;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const uint32_t col = TPL * (4u * g + k);
-            if (col >= p.Dv) continue;
-            float v[TPL];
-#pragma unroll
-            for (int t = 0; t < TPL; ++t) v[t] = acc[t][k] * inv;
-            if constexpr (OUT_BF16) {
-                using bf2 = __bf16 __attribute__((ext_vector_type(2)));
-                uint32_t o[TPL / 2];
-#pragma unroll
-                for (int w = 0; w < TPL / 2; ++w)  // v_cvt_pk_bf16_f32, as mispmm_f32_to_bf16: RNE, a NaN stays a NaN
-                    o[w] = __builtin_bit_cast(uint32_t, bf2{static_cast<__bf16>(v[2 * w]), static_cast<__bf16>(v[2 * w + 1])});
-                uint16_t *dst = static_cast<uint16_t *>(out) + base + col;
-                if constexpr (TPL == 8) *reinterpret_cast<u32x4_t *>(dst) = u32x4_t{o[0], o[1], o[2], o[3]};
-                else *reinterpret_cast<u32x2_t *>(dst) = u32x2_t{o[0], o[1]};
-            } else {
-                float *dst = static_cast<float *>(out) + base + col;
-#pragma unroll
-                for (int w = 0; w < TPL / 4; ++w) *reinterpret_cast<f32x4_t *>(dst + 4 * w) = f32x4_t{v[4 * w], v[4 * w + 1], v[4 * w + 2], v[4 * w + 3]};
-            }
+            if (col < p.Dv) store_run<TPL>(acc, k, inv, out, base, col, OUT_BF16);
         }
         if (lse_out && g == 0) lse_out[static_cast<size_t>(h) * p.rows + row] = lse;
     };
@@ -130,15 +82,7 @@ __global__ void __launch_bounds__(64 * kAttnWaves)
         return;
     }
 
-    // the accumulators, settled: see the header
-    auto settle = [&] {
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (TPL == 8)
-            asm volatile("s_nop 15" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]), "+v"(acc[6]), "+v"(acc[7]));
-        else
-            asm volatile("s_nop 15" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    auto settle_acc = [&] { settle<TPL>(acc); };  // a lambda, like store: through a plain call the step's ISA moves
 
     const rsrc_t qr = make_rsrc(Q + h * p.q_head, p.q_bytes), kr = make_rsrc(K + h * p.k_head, p.k_bytes), vr = make_rsrc(V + h * p.v_head, p.v_bytes);
     const uint32_t kcol = g * 8u;  // the lane's 8 columns of a 32-column step of D
@@ -146,10 +90,7 @@ __global__ void __launch_bounds__(64 * kAttnWaves)
 #pragma unroll
     for (int s = 0; s < DS; ++s) qf[s] = load_frag(qr, row * p.ldq2, s * 32u + kcol, p.D);  // < 2 GiB: the host declines anything larger
 
-    // The lane's share of a load's offset does not change along the row: row i (K) resp. 4g + j (V) of a 16-key tile and the
-    // lane's columns, or the dropped-load mark for columns at or past D / Dv.  The tile's first key comes as the wave-uniform
-    // scalar offset.  A tile that is not there -- a block column at or past K / bS, the missing half of a half step, a step
-    // past the row's end -- takes the mark as the whole vector offset and a scalar offset of 0 (two marks added would wrap).
+    // the lane's share of the offsets of K's fragments and of V in the V layout (attn_bsr_tiles.hpp, LOADS)
     uint32_t koff[DS], voff[4];
 #pragma unroll
     for (int s = 0; s < DS; ++s) koff[s] = s * 32u + kcol < p.D ? i * p.ldk2 + (s * 32u + kcol) * 2u : kDropLoad;
@@ -173,12 +114,12 @@ __global__ void __launch_bounds__(64 * kAttnWaves)
             return Cols{e < be ? ca : 0xFFFFFFFFu, e < be ? ca : 0xFFFFFFFFu};
         }
     };
-    constexpr uint32_t kSecond = BS == 32 ? 16u : 0u;  // first key of the second tile inside its block
+    constexpr uint32_t kSecond = W::kSecond, EPS = W::EPS;
     // everything a step reads, fetched one step ahead: K fragments, the mask's elements, V's rows
     struct Stage {
         bf16x8_t k[2][DS];
         f32x4_t ma, mb;
-        uint32_t v[8][TPL / 2];  // slot j < 4: key 4g + j of the first tile; slot 4 + j: key 4g + j of the second
+        TRows<TPL> v;
     };
     auto load_stage = [&](Cols c, uint32_t e, Stage &st) {
         const bool va = c.a < p.Kb, vb = c.b < p.Kb;  // wave-uniform
@@ -195,18 +136,7 @@ __global__ void __launch_bounds__(64 * kAttnWaves)
             st.mb = *reinterpret_cast<const f32x4_t *>(mask + eb + mask_at);
         }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint32_t vo = (j < 4 ? va : vb) ? voff[j & 3] : kDropLoad, so = (j < 4 ? ra : rb) * p.ldv2;
-            if constexpr (TPL == 8) {
-                const auto r = __builtin_amdgcn_raw_buffer_load_b128(vr, vo, so, 0);
-#pragma unroll
-                for (int w = 0; w < 4; ++w) st.v[j][w] = r[w];
-            } else {
-                const auto r = __builtin_amdgcn_raw_buffer_load_b64(vr, vo, so, 0);
-                st.v[j][0] = r[0];
-                st.v[j][1] = r[1];
-            }
-        }
+        for (int j = 0; j < 8; ++j) load_trow<TPL>(st.v, j, vr, (j < 4 ? va : vb) ? voff[j & 3] : kDropLoad, (j < 4 ? ra : rb) * p.ldv2);
     };
 
     float m = ninf, mu = 0.f, l = 0.f, lx = 0.f;
@@ -225,14 +155,8 @@ __global__ void __launch_bounds__(64 * kAttnWaves)
         float z[8];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if constexpr (MASK) {
-                z[j] = __builtin_fmaf(p.scale, sa[j], use.ma[j]);
-                z[4 + j] = __builtin_fmaf(p.scale, sb[j], use.mb[j]);
-            } else {
-                z[j] = p.scale * sa[j];
-                z[4 + j] = p.scale * sb[j];
-            }
-            if (!second) z[4 + j] = ninf;
+            z[j] = scaled<MASK>(p.scale, sa[j], use.ma, j);
+            z[4 + j] = second ? scaled<MASK>(p.scale, sb[j], use.mb, j) : ninf;
         }
         float mx = z[0];
 #pragma unroll
@@ -241,15 +165,14 @@ __global__ void __launch_bounds__(64 * kAttnWaves)
         mx = __builtin_fmaxf(mx, lane_xor<32>(mx));
         const float m_new = __builtin_fmaxf(m, mx);
         const float mu_new = __builtin_fabsf(m_new) == __builtin_huge_valf() ? 0.f : m_new;
-        const float alpha = m == ninf ? 1.f : attn_exp(mu - mu_new);
+        const float alpha = m == ninf ? 1.f : tile_exp(mu - mu_new);
         m = m_new;
         mu = mu_new;
-        using bf2 = __bf16 __attribute__((ext_vector_type(2)));
         u32x4_t pw;
         float t = 0.f, tx = 0.f;
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
-            const float p0 = attn_exp(z[2 * w] - mu), p1 = attn_exp(z[2 * w + 1] - mu);
+            const float p0 = tile_exp(z[2 * w] - mu), p1 = tile_exp(z[2 * w + 1] - mu);
             pw[w] = __builtin_bit_cast(uint32_t, bf2{static_cast<__bf16>(p0), static_cast<__bf16>(p1)});
             t = t + __uint_as_float(pw[w] << 16);
             t = t + __uint_as_float(pw[w] & 0xFFFF0000u);
@@ -258,23 +181,12 @@ __global__ void __launch_bounds__(64 * kAttnWaves)
         }
         l = l * alpha + t;
         lx = lx * alpha + tx;
-        settle();
+        settle_acc();
 #pragma unroll
         for (int tt = 0; tt < TPL; ++tt) acc[tt] = acc[tt] * alpha;
         const bf16x8_t pfrag = __builtin_bit_cast(bf16x8_t, pw);
 #pragma unroll
-        for (int w = 0; w < TPL / 2; ++w) {
-            // tiles 2w and 2w + 1 take the low and high bf16 of dword w of every key's V columns
-            u32x4_t even, odd;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t lo = use.v[2 * q][w], hi = use.v[2 * q + 1][w];
-                even[q] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);  // {hi.h0, lo.h0}
-                odd[q] = __builtin_amdgcn_perm(hi, lo, 0x07060302u);   // {hi.h1, lo.h1}
-            }
-            acc[2 * w] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, even), pfrag, acc[2 * w], 0, 0, 0);
-            acc[2 * w + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, odd), pfrag, acc[2 * w + 1], 0, 0, 0);
-        }
+        for (int w = 0; w < TPL / 2; ++w) mfma_trow_pair<TPL>(acc[2 * w], acc[2 * w + 1], use.v, w, pfrag);
         nxt = after;
         e += EPS;
     };
@@ -293,7 +205,7 @@ __global__ void __launch_bounds__(64 * kAttnWaves)
     l = l + lane_xor<32>(l);
     lx = lx + lane_xor<16>(lx);
     lx = lx + lane_xor<32>(lx);
-    settle();
+    settle_acc();
     store(1.f / l, mu + __builtin_logf(lx));
 }
 
@@ -311,18 +223,11 @@ struct AttnCall {
 template <int BS, int DS, int TPL, bool MASK, bool OUT_BF16>
 void launch_attn(const AttnCall &c) {
     AttnParams p = c.p;
-    p.units = c.Mb * (BS / 16);
-    p.wgs_per_head = ceil_div(p.units, kAttnWaves);
-    p.total = p.wgs_per_head * c.H;
-    const XcdGrid xg = xcd_grid(p.total);
-    p.xcd_chunk = xg.chunk;
+    const uint32_t grid = finish_grid(p, c.Mb * (BS / 16), c.H);
     note_kernel("attn_bsr<b%d,%s,%s,D%d,T%d>", BS, OUT_BF16 ? "bf16" : "f32", MASK ? "mask" : "nomask", DS, TPL);
-    hipLaunchKernelGGL((attn_bsr_kernel<BS, DS, TPL, MASK, OUT_BF16>), dim3(xg.grid), dim3(64 * kAttnWaves), 0, c.stream, p, c.blockRowPtrs,
+    hipLaunchKernelGGL((attn_bsr_kernel<BS, DS, TPL, MASK, OUT_BF16>), dim3(grid), dim3(64 * kTileWaves), 0, c.stream, p, c.blockRowPtrs,
                        c.blockColIdxs, c.Q, c.K, c.V, c.mask, c.out, c.lse);
 }
-
-// elements one head's rows span: the last row ends with its last column, not with its stride
-uint64_t span(uint64_t rows, uint32_t ld, uint32_t width) { return rows == 0 ? 0 : (rows - 1) * ld + width; }
 
 }  // namespace
 
@@ -335,12 +240,7 @@ extern "C" int mispmm_attn_bsr_bf16(mispmm_stream_t stream, uint32_t H, uint32_t
                                     uint64_t q_head, const uint16_t *Kmat, uint32_t ldk, uint64_t k_head, const uint16_t *V, uint32_t ldv,
                                     uint64_t v_head, uint32_t D, uint32_t Dv, const float *mask, float scale, void *out, uint32_t ldo,
                                     uint64_t o_head, int out_bf16, float *lse) {
-    if (bS != 16 && bS != 32) return fail(MISPMM_ERR_UNSUPPORTED, "attn_bsr_bf16: only 16x16 or 32x32 blocks (got bS=%u)", bS);
-    if (!(scale > 0.f) || scale == __builtin_huge_valf())
-        return fail(MISPMM_ERR_INVALID_ARG, "attn_bsr_bf16: scale must be finite and > 0 (got %g)", static_cast<double>(scale));
-    if (D == 0 || Dv == 0 || D % 8 != 0 || Dv % 8 != 0 || D > 128 || Dv > 128)
-        return fail(MISPMM_ERR_UNSUPPORTED, "attn_bsr_bf16: D and Dv must be multiples of 8 from 8 to 128 (got D=%u Dv=%u)", D, Dv);
-    if (K % bS != 0) return fail(MISPMM_ERR_INVALID_ARG, "attn_bsr_bf16: K=%u is not a multiple of the block size %u", K, bS);
+    if (const int refused = refuse_shape("attn_bsr_bf16", bS, scale, D, Dv, K)) return refused;
     if (H == 0 || numBlockRows == 0) return MISPMM_OK;
     if (!blockRowPtrs || !Q || !Kmat || !V || !out || (numBlocks != 0 && !blockColIdxs))
         return fail(MISPMM_ERR_INVALID_ARG, "attn_bsr_bf16: blockRowPtrs, blockColIdxs, Q, K, V or out is null");
@@ -362,7 +262,7 @@ extern "C" int mispmm_attn_bsr_bf16(mispmm_stream_t stream, uint32_t H, uint32_t
     if (qs > 0x7FFFFFFFull || ks > 0x7FFFFFFFull || vs > 0x7FFFFFFFull)
         return fail(MISPMM_ERR_UNSUPPORTED, "attn_bsr_bf16: Q, K or V of one head spans 2 GiB or more (%llu, %llu, %llu bytes)",
                     static_cast<unsigned long long>(qs), static_cast<unsigned long long>(ks), static_cast<unsigned long long>(vs));
-    if (rows > 0x7FFFFFFFull || ceil_div64(rows / 16, kAttnWaves) * H > 0x7FFFFFFFull)
+    if (rows > 0x7FFFFFFFull || ceil_div64(rows / 16, kTileWaves) * H > 0x7FFFFFFFull)
         return fail(MISPMM_ERR_UNSUPPORTED, "attn_bsr_bf16: %llu rows x %u heads are more work units than one launch takes",
                     static_cast<unsigned long long>(rows), H);
     AttnCall c{};

@@ -7,14 +7,14 @@
 //   dS         = fl(fl(P * fl(dP - delta[r])) * scale)    delta[r] = sum_c dO[r][c] * O[r][c]
 //   dQ[r]      = sum_key bf16(dS) K[key]      dK[key] = sum_r bf16(dS) Q[r]      dV[key] = sum_r bf16(P) dO[r]
 //
-// THE ROW PASS is the forward's kernel turned round.  One wave owns 16 query rows of one head and walks its block row 32 keys
-// at a step.  Q's and dO's fragments stay in registers; both score products are computed transposed (K rows resp. V rows are
-// the A operand), so lane (i = l & 15, g = l >> 4) holds query i x keys 4g .. 4g + 3 of both 16-key tiles for S AND dP: lse[i]
-// and delta[i] are lane-local and dS needs no cross-lane move.  dQ^T += K^T dS^T is the forward's O^T += V^T P^T: K is read a
-// second time in the forward's V layout (for the lane's 8 keys, the TPL consecutive columns TPL * i ..) and regrouped with
-// v_perm_b32; the store is the forward's.  Before the walk the wave forms delta of its 16 rows from the dO fragments it holds
-// and the same columns of O (a lane sum by fma, columns ascending, then (g0 + g1) + (g2 + g3) by two xor moves) and writes
-// it to the caller's workspace.  Without dQ the pass stops there.
+// Work unit, lane layout of the transposed products, the V layout, loads and settle(): ../attn_bsr_tiles.hpp.
+//
+// THE ROW PASS.  One wave owns 16 query rows of one head and walks its block row 32 keys at a step.  Q's and dO's fragments
+// stay in registers; K rows resp. V rows are the A operands of the two score products, so lane (i, g) holds query i x keys
+// 4g .. 4g + 3 of both 16-key tiles for S AND dP: lse[i] and delta[i] are lane-local and dS needs no cross-lane move.
+// dQ^T += K^T dS^T: K is read a second time in the V layout.  Before the walk the wave forms delta of its 16 rows from the dO
+// fragments it holds and the same columns of O (a lane sum by fma, columns ascending, then (g0 + g1) + (g2 + g3) by two xor
+// moves) and writes it to the caller's workspace.  Without dQ the pass stops there.
 //
 // THE COLUMN PASS is its mirror on A^T's pattern.  One wave owns 16 keys of one head, holds their K and V fragments as the B
 // operands (the lane then holds key i x queries 4g .. 4g + 3) and walks the block column 32 queries at a step: Q and dO rows
@@ -24,22 +24,14 @@
 //
 // One register stage: a step's loads are issued together at its top and the MFMAs wait for them; the latency is left to the
 // other waves of the SIMD (two stages do not fit at D = Dv = 128).  The accumulators are only
-// ever touched by MFMAs inside the loop, so the XDL-write to VALU-read wait settle() spells out (attn_bsr.hip) is needed
+// ever touched by MFMAs inside the loop, so the XDL-write to VALU-read wait settle() spells out is needed
 // once: on the edge out of the loop, before the store.  No LDS, no barrier, no atomics; every sum has a fixed order.
-#include "lane_moves.hpp"
+#include "../attn_bsr_tiles.hpp"
 #include "mispmm_attn_bwd.h"
 
 namespace mispmm {
 
 namespace {
-
-using bf16x8_t = short __attribute__((ext_vector_type(8)));
-using f32x4_t = float __attribute__((ext_vector_type(4)));
-using u32x2_t = uint32_t __attribute__((ext_vector_type(2)));
-using u32x4_t = uint32_t __attribute__((ext_vector_type(4)));
-using bf2 = __bf16 __attribute__((ext_vector_type(2)));
-
-constexpr int kBwdWaves = 4;
 
 struct BwdParams {
     uint32_t units, wgs_per_head, total, xcd_chunk;  // units: 16-row (16-key) work units of one head
@@ -51,90 +43,6 @@ struct BwdParams {
     float scale;
     uint64_t q_head, k_head, v_head, g_head, o_head, dq_head, dk_head, dv_head;  // elements
 };
-
-__device__ __forceinline__ float bwd_exp(float t) { return __builtin_amdgcn_exp2f(t * 1.44269504088896340736f); }  // as attn_bsr.hip
-
-__device__ __forceinline__ bf16x8_t load_frag(rsrc_t rsrc, uint32_t row_off, uint32_t col, uint32_t N) {
-    const uint32_t off = col < N ? row_off + col * 2u : kDropLoad;
-    return __builtin_bit_cast(bf16x8_t, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
-}
-
-// the accumulators, settled: every read after this statement follows the MFMAs that wrote them by 16 cycles (attn_bsr.hip)
-template <int TPL>
-__device__ __forceinline__ void settle(f32x4_t (&acc)[TPL]) {
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TPL == 8)
-        asm volatile("s_nop 15" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]), "+v"(acc[6]), "+v"(acc[7]));
-    else
-        asm volatile("s_nop 15" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-// lane (i, g) holds X[row][TPL (4g + k) + t] in acc[t][k]: for every k a run of TPL consecutive columns, inside `width` or
-// past it together (a multiple of 8).  fp32, or bf16 by v_cvt_pk_bf16_f32 (RNE, a NaN stays a NaN).
-template <int TPL>
-__device__ __forceinline__ void store_tiles(const f32x4_t (&acc)[TPL], void *out, size_t base, uint32_t g, uint32_t width, bool as_bf16) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t col = TPL * (4u * g + k);
-        if (col >= width) continue;
-        float v[TPL];
-#pragma unroll
-        for (int t = 0; t < TPL; ++t) v[t] = acc[t][k];
-        if (as_bf16) {
-            uint32_t o[TPL / 2];
-#pragma unroll
-            for (int w = 0; w < TPL / 2; ++w)
-                o[w] = __builtin_bit_cast(uint32_t, bf2{static_cast<__bf16>(v[2 * w]), static_cast<__bf16>(v[2 * w + 1])});
-            uint16_t *dst = static_cast<uint16_t *>(out) + base + col;
-            if constexpr (TPL == 8) *reinterpret_cast<u32x4_t *>(dst) = u32x4_t{o[0], o[1], o[2], o[3]};
-            else *reinterpret_cast<u32x2_t *>(dst) = u32x2_t{o[0], o[1]};
-        } else {
-            float *dst = static_cast<float *>(out) + base + col;
-#pragma unroll
-            for (int w = 0; w < TPL / 4; ++w) *reinterpret_cast<f32x4_t *>(dst + 4 * w) = f32x4_t{v[4 * w], v[4 * w + 1], v[4 * w + 2], v[4 * w + 3]};
-        }
-    }
-}
-
-// the lane's rows of an operand in the V layout of attn_bsr.hip: slot j < 4 row 4g + j of the first 16-row tile, slot 4 + j
-// the same row of the second; of each the TPL consecutive bf16 from column TPL * i
-template <int TPL>
-struct TRows {
-    uint32_t v[8][TPL / 2];
-};
-template <int TPL>
-__device__ __forceinline__ void load_trows(TRows<TPL> &t, rsrc_t rsrc, const uint32_t (&off)[4], bool va, bool vb, uint32_t sa, uint32_t sb) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint32_t vo = (j < 4 ? va : vb) ? off[j & 3] : kDropLoad, so = j < 4 ? sa : sb;
-        if constexpr (TPL == 8) {
-            const auto r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo, so, 0);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) t.v[j][w] = r[w];
-        } else {
-            const auto r = __builtin_amdgcn_raw_buffer_load_b64(rsrc, vo, so, 0);
-            t.v[j][0] = r[0];
-            t.v[j][1] = r[1];
-        }
-    }
-}
-// acc^T += X^T * W: tiles 2w and 2w + 1 take the low and high bf16 of dword w of every row's columns (attn_bsr.hip)
-template <int TPL>
-__device__ __forceinline__ void mfma_trows(f32x4_t (&acc)[TPL], const TRows<TPL> &t, bf16x8_t w8) {
-#pragma unroll
-    for (int w = 0; w < TPL / 2; ++w) {
-        u32x4_t even, odd;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t lo = t.v[2 * q][w], hi = t.v[2 * q + 1][w];
-            even[q] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);  // {hi.h0, lo.h0}
-            odd[q] = __builtin_amdgcn_perm(hi, lo, 0x07060302u);   // {hi.h1, lo.h1}
-        }
-        acc[2 * w] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, even), w8, acc[2 * w], 0, 0, 0);
-        acc[2 * w + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, odd), w8, acc[2 * w + 1], 0, 0, 0);
-    }
-}
 
 // the weights and dS of the lane's 8 elements of a step, as the two bf16 B operands.  ls / dl: lse and delta of the
 // element's query; a tile that is not there contributes +0.
@@ -148,7 +56,7 @@ __device__ __forceinline__ void weights(const float (&z)[8], const float (&dp)[8
         for (int u = 0; u < 2; ++u) {
             const int j = 2 * w + u;
             const bool there = j < 4 ? first : second;  // wave-uniform
-            const float pj = bwd_exp(z[j] - ls[j]);
+            const float pj = tile_exp(z[j] - ls[j]);
             const float t = dp[j] - dl[j];
             pv[u] = there ? pj : 0.f;
             dv[u] = there ? (pj * t) * scale : 0.f;
@@ -162,22 +70,22 @@ __device__ __forceinline__ void weights(const float (&z)[8], const float (&dp)[8
 
 // BS: block size.  DS / DSV: 32-column steps of D / Dv held (D <= 32 DS, Dv <= 32 DSV); dQ has 2 DS accumulator tiles.
 template <int BS, int DS, int DSV, bool MASK>
-__global__ void __launch_bounds__(64 * kBwdWaves)
+__global__ void __launch_bounds__(64 * kTileWaves)
     attn_bwd_rows_kernel(const BwdParams p, const uint32_t *__restrict__ blockRowPtrs, const uint32_t *__restrict__ blockColIdxs,
                          const uint16_t *__restrict__ Q, const uint16_t *__restrict__ K, const uint16_t *__restrict__ V, const uint16_t *__restrict__ G,
                          const void *__restrict__ O, const float *__restrict__ lse, const float *__restrict__ mask, float *__restrict__ delta,
                          void *__restrict__ dQ) {
-    constexpr uint32_t T = BS / 16;
-    constexpr uint32_t EPS = BS == 16 ? 2 : 1;
+    using W = Walk<BS>;
+    constexpr uint32_t EPS = W::EPS, kSecond = W::kSecond;
     constexpr int TPL = 2 * DS;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t item = xcd_block(blockIdx.x, p.xcd_chunk);
     if (item >= p.total) return;
     const uint32_t h = item / p.wgs_per_head;
-    const uint32_t unit = (item - h * p.wgs_per_head) * kBwdWaves + wave;
+    const uint32_t unit = (item - h * p.wgs_per_head) * kTileWaves + wave;
     if (unit >= p.units) return;
-    const uint32_t R = unit / T, sub = unit % T;
+    const uint32_t R = unit / W::T, sub = unit % W::T;
     const uint32_t i = lane & 15, g = lane >> 4;
     const uint32_t row = unit * 16u + i;  // < rows
     const uint32_t kcol = g * 8u;         // the lane's 8 columns of a 32-column step
@@ -228,7 +136,7 @@ __global__ void __launch_bounds__(64 * kBwdWaves)
     const size_t dq_at = static_cast<size_t>(h) * p.dq_head + static_cast<size_t>(row) * p.lddq;
     const uint32_t bs = blockRowPtrs[R], be = blockRowPtrs[R + 1];
     if (be <= bs) {  // an empty block row: +0 rows
-        store_tiles<TPL>(acc, dQ, dq_at, g, p.D, p.grads_bf16 != 0);
+        store_tiles<TPL>(acc, dQ, dq_at, g, p.D, 1.f, p.grads_bf16 != 0);
         return;
     }
 
@@ -238,7 +146,7 @@ __global__ void __launch_bounds__(64 * kBwdWaves)
     for (int s = 0; s < DS; ++s) qf[s] = load_frag(qr, row * p.ldq2, s * 32u + kcol, p.D);
     const float ls = lse[static_cast<size_t>(h) * p.rows + row];
 
-    // the lane's share of a load's offset (attn_bsr.hip): row i of a 16-key tile and the lane's columns for the A operands of
+    // the lane's share of a load's offset (attn_bsr_tiles.hpp, LOADS): row i of a 16-key tile and the lane's columns for the A operands of
     // the two score products, rows 4g + j and columns TPL * i .. for K in the V layout
     uint32_t koff[DS], voff[DSV], ktoff[4];
 #pragma unroll
@@ -249,7 +157,6 @@ __global__ void __launch_bounds__(64 * kBwdWaves)
 #pragma unroll
     for (int j = 0; j < 4; ++j) ktoff[j] = tcol < p.D ? (4u * g + j) * p.ldk2 + tcol * 2u : kDropLoad;
     const size_t mask_at = static_cast<size_t>(sub * 16u + i) * BS + 4u * g;
-    constexpr uint32_t kSecond = BS == 32 ? 16u : 0u;
     const uint32_t last = be - 1;
     float lsv[8], dlv[8];
 #pragma unroll
@@ -293,13 +200,8 @@ __global__ void __launch_bounds__(64 * kBwdWaves)
         float z[8], dp[8];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if constexpr (MASK) {
-                z[j] = __builtin_fmaf(p.scale, sa[j], ma[j]);
-                z[4 + j] = __builtin_fmaf(p.scale, sb[j], mb[j]);
-            } else {
-                z[j] = p.scale * sa[j];
-                z[4 + j] = p.scale * sb[j];
-            }
+            z[j] = scaled<MASK>(p.scale, sa[j], ma, j);
+            z[4 + j] = scaled<MASK>(p.scale, sb[j], mb, j);
             dp[j] = da[j];
             dp[4 + j] = db[j];
         }
@@ -308,27 +210,27 @@ __global__ void __launch_bounds__(64 * kBwdWaves)
         mfma_trows<TPL>(acc, kt, dsfrag);
     }
     settle<TPL>(acc);
-    store_tiles<TPL>(acc, dQ, dq_at, g, p.D, p.grads_bf16 != 0);
+    store_tiles<TPL>(acc, dQ, dq_at, g, p.D, 1.f, p.grads_bf16 != 0);
 }
 
 // the mirror on A^T's pattern: one wave owns 16 keys; dK has 2 DS accumulator tiles, dV 2 DSV
 template <int BS, int DS, int DSV, bool MASK>
-__global__ void __launch_bounds__(64 * kBwdWaves)
+__global__ void __launch_bounds__(64 * kTileWaves)
     attn_bwd_cols_kernel(const BwdParams p, const uint32_t *__restrict__ tRowPtrs, const uint32_t *__restrict__ tColIdxs,
                          const uint32_t *__restrict__ perm, const uint16_t *__restrict__ Q, const uint16_t *__restrict__ K,
                          const uint16_t *__restrict__ V, const uint16_t *__restrict__ G, const float *__restrict__ lse, const float *__restrict__ delta,
                          const float *__restrict__ mask, void *__restrict__ dK, void *__restrict__ dV) {
-    constexpr uint32_t T = BS / 16;
-    constexpr uint32_t EPS = BS == 16 ? 2 : 1;
+    using W = Walk<BS>;
+    constexpr uint32_t EPS = W::EPS, kSecond = W::kSecond;
     constexpr int TK = 2 * DS, TV = 2 * DSV;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t item = xcd_block(blockIdx.x, p.xcd_chunk);
     if (item >= p.total) return;
     const uint32_t h = item / p.wgs_per_head;
-    const uint32_t unit = (item - h * p.wgs_per_head) * kBwdWaves + wave;
+    const uint32_t unit = (item - h * p.wgs_per_head) * kTileWaves + wave;
     if (unit >= p.units) return;
-    const uint32_t C = unit / T, sub = unit % T;
+    const uint32_t C = unit / W::T, sub = unit % W::T;
     const uint32_t i = lane & 15, g = lane >> 4;
     const uint32_t key = unit * 16u + i;  // < Kb * bS
     const uint32_t kcol = g * 8u;
@@ -360,8 +262,7 @@ __global__ void __launch_bounds__(64 * kBwdWaves)
             qtoff[j] = i * TK < p.D ? (4u * g + j) * p.ldq2 + i * TK * 2u : kDropLoad;
             gtoff[j] = i * TV < p.Dv ? (4u * g + j) * p.ldg2 + i * TV * 2u : kDropLoad;
         }
-        constexpr uint32_t kSecond = BS == 32 ? 16u : 0u;
-        const uint32_t last = be - 1;
+            const uint32_t last = be - 1;
         const float *lse_h = lse + static_cast<size_t>(h) * p.rows + 4u * g;
         const float *delta_h = delta + static_cast<size_t>(h) * p.rows + 4u * g;
         const size_t mask_at = static_cast<size_t>(4u * g) * BS + sub * 16u + i;  // query 4g, key i of the wave's half
@@ -424,13 +325,8 @@ __global__ void __launch_bounds__(64 * kBwdWaves)
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if constexpr (MASK) {
-                    z[j] = __builtin_fmaf(p.scale, sa[j], mk[j]);
-                    z[4 + j] = __builtin_fmaf(p.scale, sb[j], mk[4 + j]);
-                } else {
-                    z[j] = p.scale * sa[j];
-                    z[4 + j] = p.scale * sb[j];
-                }
+                z[j] = scaled<MASK>(p.scale, sa[j], mk, j);
+                z[4 + j] = scaled<MASK>(p.scale, sb[j], mk, 4 + j);
                 dp[j] = da[j];
                 dp[4 + j] = db[j];
                 if (!want_dk) dlv[j] = 0.f, dlv[4 + j] = 0.f;
@@ -444,8 +340,8 @@ __global__ void __launch_bounds__(64 * kBwdWaves)
         if (want_dv) settle<TV>(accv);
     }
     // an empty block column: +0 rows
-    if (want_dk) store_tiles<TK>(acck, dK, dk_at, g, p.D, p.grads_bf16 != 0);
-    if (want_dv) store_tiles<TV>(accv, dV, dv_at, g, p.Dv, p.grads_bf16 != 0);
+    if (want_dk) store_tiles<TK>(acck, dK, dk_at, g, p.D, 1.f, p.grads_bf16 != 0);
+    if (want_dv) store_tiles<TV>(accv, dV, dv_at, g, p.Dv, 1.f, p.grads_bf16 != 0);
 }
 
 struct BwdCall {
@@ -460,34 +356,21 @@ struct BwdCall {
     void *dQ, *dK, *dV;
 };
 
-void finish_grid(BwdParams &p, uint32_t units, uint32_t H) {
-    p.units = units;
-    p.wgs_per_head = ceil_div(units, kBwdWaves);
-    p.total = p.wgs_per_head * H;
-}
-
 template <int BS, int DS, int DSV, bool MASK>
 void launch_rows(const BwdCall &c) {
     BwdParams p = c.p;
-    finish_grid(p, p.Mb * (BS / 16), c.H);
-    const XcdGrid xg = xcd_grid(p.total);
-    p.xcd_chunk = xg.chunk;
-    hipLaunchKernelGGL((attn_bwd_rows_kernel<BS, DS, DSV, MASK>), dim3(xg.grid), dim3(64 * kBwdWaves), 0, c.stream, p, c.rowPtrs, c.colIdxs, c.Q, c.K,
+    const uint32_t grid = finish_grid(p, p.Mb * (BS / 16), c.H);
+    hipLaunchKernelGGL((attn_bwd_rows_kernel<BS, DS, DSV, MASK>), dim3(grid), dim3(64 * kTileWaves), 0, c.stream, p, c.rowPtrs, c.colIdxs, c.Q, c.K,
                        c.V, c.G, c.O, c.lse, c.mask, c.delta, c.dQ);
 }
 
 template <int BS, int DS, int DSV, bool MASK>
 void launch_cols(const BwdCall &c) {
     BwdParams p = c.p;
-    finish_grid(p, p.Kb * (BS / 16), c.H);
-    const XcdGrid xg = xcd_grid(p.total);
-    p.xcd_chunk = xg.chunk;
-    hipLaunchKernelGGL((attn_bwd_cols_kernel<BS, DS, DSV, MASK>), dim3(xg.grid), dim3(64 * kBwdWaves), 0, c.stream, p, c.tRowPtrs, c.tColIdxs, c.perm,
+    const uint32_t grid = finish_grid(p, p.Kb * (BS / 16), c.H);
+    hipLaunchKernelGGL((attn_bwd_cols_kernel<BS, DS, DSV, MASK>), dim3(grid), dim3(64 * kTileWaves), 0, c.stream, p, c.tRowPtrs, c.tColIdxs, c.perm,
                        c.Q, c.K, c.V, c.G, c.lse, c.delta, c.mask, c.dK, c.dV);
 }
-
-// elements one head's rows span: the last row ends with its last column, not with its stride
-uint64_t span(uint64_t rows, uint32_t ld, uint32_t width) { return rows == 0 ? 0 : (rows - 1) * ld + width; }
 
 }  // namespace
 
@@ -503,12 +386,7 @@ extern "C" int mispmm_attn_bsr_bwd_bf16(mispmm_stream_t stream, uint32_t H, uint
                                         int out_bf16, const float *lse, float *delta, uint32_t D, uint32_t Dv, const float *mask, float scale,
                                         void *dQ, uint32_t lddq, uint64_t dq_head, void *dK, uint32_t lddk, uint64_t dk_head, void *dV,
                                         uint32_t lddv, uint64_t dv_head, int grads_bf16) {
-    if (bS != 16 && bS != 32) return fail(MISPMM_ERR_UNSUPPORTED, "attn_bsr_bwd_bf16: only 16x16 or 32x32 blocks (got bS=%u)", bS);
-    if (!(scale > 0.f) || scale == __builtin_huge_valf())
-        return fail(MISPMM_ERR_INVALID_ARG, "attn_bsr_bwd_bf16: scale must be finite and > 0 (got %g)", static_cast<double>(scale));
-    if (D == 0 || Dv == 0 || D % 8 != 0 || Dv % 8 != 0 || D > 128 || Dv > 128)
-        return fail(MISPMM_ERR_UNSUPPORTED, "attn_bsr_bwd_bf16: D and Dv must be multiples of 8 from 8 to 128 (got D=%u Dv=%u)", D, Dv);
-    if (K % bS != 0) return fail(MISPMM_ERR_INVALID_ARG, "attn_bsr_bwd_bf16: K=%u is not a multiple of the block size %u", K, bS);
+    if (const int refused = refuse_shape("attn_bsr_bwd_bf16", bS, scale, D, Dv, K)) return refused;
     if (H == 0 || numBlockRows == 0 || (!dQ && !dK && !dV)) return MISPMM_OK;
     const bool rows_pass = dQ || dK, cols_pass = (dK || dV) && K != 0;
     if (!blockRowPtrs || !Q || !Kmat || !V || !dO || !lse || (numBlocks != 0 && !blockColIdxs))
@@ -546,7 +424,7 @@ extern "C" int mispmm_attn_bsr_bwd_bf16(mispmm_stream_t stream, uint32_t H, uint
                         static_cast<unsigned long long>(qs), static_cast<unsigned long long>(ks), static_cast<unsigned long long>(vs),
                         static_cast<unsigned long long>(gs), static_cast<unsigned long long>(os), static_cast<unsigned long long>(dqs),
                         static_cast<unsigned long long>(dks), static_cast<unsigned long long>(dvs));
-    if (rows > 0x7FFFFFFFull || ceil_div64(rows / 16, kBwdWaves) * H > 0x7FFFFFFFull || ceil_div64(K / 16, kBwdWaves) * H > 0x7FFFFFFFull)
+    if (rows > 0x7FFFFFFFull || ceil_div64(rows / 16, kTileWaves) * H > 0x7FFFFFFFull || ceil_div64(K / 16, kTileWaves) * H > 0x7FFFFFFFull)
         return fail(MISPMM_ERR_UNSUPPORTED, "attn_bsr_bwd_bf16: %llu rows or %u keys x %u heads are more work units than one launch takes",
                     static_cast<unsigned long long>(rows), K, H);
     BwdCall c{};
