@@ -36,9 +36,13 @@ Both gradients come back in bfloat16.  The CSR product with fp32 values and the 
     out = sparse_attention_bf16(a, q, k, v)            # bfloat16 q, k, v: one launch (attn_csr_bf16.attention_csr_bf16); the
                                                        # backward is ops.attention_csr_bwd on the widened operands
 
-Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, a fused CSR attention backward that reads bf16 itself,
-a gradient for the fused CSR attention's bias, the column-compacted block layouts (their tiles are built on the host from the
-values), a device kernel for the blocks[perm] transpose."""
+    out = sparse_attention(a, q, k, v, bias=b, bias_grad=True, fused=True, fused_backward=True)   # a TRAINED bias over A's entries
+                                                       # ([nnz] or [H, nnz]): b.grad by one more launch for all heads
+                                                       # (attn_csr_dbias.attention_csr_dbias); every other path takes the keyword too
+
+Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, a head-summed bias gradient from the kernel (a bias
+shared by the heads gets the per-head result summed by torch), the column-compacted block layouts (their tiles are built on the
+host from the values), a device kernel for the blocks[perm] transpose."""
 import dataclasses
 from dataclasses import dataclass
 
@@ -180,13 +184,24 @@ def edge_softmax(a, scores, acc="reference"):
     return _EdgeSoftmax.apply(scores, a, acc)
 
 
+def _bias_grad(per_head, bias):
+    """The gradient of `bias` from the per-head result ([nnz] for 2-D operands, [H, nnz]): a bias shared by the heads gets the
+    heads' sum (one torch.sum), any other one the result in its own shape.  float32 throughout."""
+    if per_head.dim() == 2 and bias.dim() == 1:
+        return torch.sum(per_head, dim=0)
+    return per_head.reshape(bias.shape)
+
+
 class _FusedSparseAttention(torch.autograd.Function):
     """The forward in one launch for all heads (ops.attention_csr).  q, k, v are saved and the weights are not: the backward
     recomputes the scores and P head by head with the FAST kernels of the four-launch forward and runs its gradient chain, so
-    the gradients are those of the unfused acc="fast" call, head by head, bit for bit."""
+    the gradients are those of the unfused acc="fast" call, head by head, bit for bit.  The chain's ds (ops.softmax_csr_bwd) is
+    the head's bias gradient: returned where the bias requires one (sparse_attention hands in a bias that does only with
+    bias_grad=True)."""
     @staticmethod
     def forward(ctx, q, k, v, a, scale, bias):
         q, k, v = q.detach(), k.detach(), v.detach()
+        bias = None if bias is None else bias.detach()
         ctx.a, ctx.scale, ctx.bias = a, scale, bias
         ctx.save_for_backward(q, k, v)
         return ops.attention_csr(a.fwd, q, k, v, scale=scale, bias=bias)
@@ -195,11 +210,12 @@ class _FusedSparseAttention(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         a, needs, scale, bias = ctx.a, ctx.needs_input_grad, ctx.scale, ctx.bias
-        if not any(needs[:3]):
+        if not any(needs[:3]) and not needs[5]:
             return (None,) * 6
         q, k, v = ctx.saved_tensors
         heads = [None] if q.dim() == 2 else range(q.shape[0])
         grads = ([], [], [])
+        grads_b = []
         for h in heads:
             qh, kh, vh, gh = (t if h is None else t[h] for t in (q, k, v, grad_out))
             bh = bias if bias is None or bias.dim() == 1 else bias[h]
@@ -211,9 +227,10 @@ class _FusedSparseAttention(torch.autograd.Function):
             grad_q = grad_k = grad_v = None
             if needs[2]:
                 grad_v = ops.spmm_csr(dataclasses.replace(a.tpattern, data=p[a.perm]), gh, acc="fast")
-            if needs[0] or needs[1]:
+            if needs[0] or needs[1] or needs[5]:
                 dp = ops.sddmm_csr(a.fwd, gh, vh, acc="fast")
                 ds = ops.softmax_csr_bwd(a.fwd, p, dp, acc="fast")
+                grads_b.append(ds)
                 if needs[0]:
                     grad_q = ops.spmm_csr(dataclasses.replace(a.fwd, data=ds), kh, acc="fast") * scale
                 if needs[1]:
@@ -221,15 +238,19 @@ class _FusedSparseAttention(torch.autograd.Function):
             for held, grad in zip(grads, (grad_q, grad_k, grad_v)):
                 held.append(grad)
         merged = [None if held[0] is None else (held[0] if q.dim() == 2 else torch.stack(held)) for held in grads]
-        return (*merged, None, None, None)
+        grad_bias = _bias_grad(grads_b[0] if q.dim() == 2 else torch.stack(grads_b), bias) if needs[5] else None
+        return (*merged, None, None, grad_bias)
 
 
 class _FusedSparseAttentionFusedBwd(torch.autograd.Function):
     """Forward and backward fused (ops.attention_csr with its lse, ops.attention_csr_bwd): q, k, v, out and lse are saved, and
-    the backward is ONE call, at most two launches for all heads, with `need` set from the inputs that require a gradient."""
+    the backward is ONE call, at most two launches for all heads, with `need` set from the inputs that require a gradient.  A
+    bias that requires a gradient gets it by one launch more (attn_csr_dbias.attention_csr_dbias), made only then; the backward
+    call is skipped where q, k and v need nothing."""
     @staticmethod
     def forward(ctx, q, k, v, a, scale, bias):
         q, k, v = q.detach(), k.detach(), v.detach()
+        bias = None if bias is None else bias.detach()
         out, lse = ops.attention_csr(a.fwd, q, k, v, scale=scale, bias=bias, return_lse=True)
         ctx.a, ctx.scale, ctx.bias = a, scale, bias
         ctx.save_for_backward(q, k, v, out, lse)
@@ -239,14 +260,19 @@ class _FusedSparseAttentionFusedBwd(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         a, needs = ctx.a, ctx.needs_input_grad
-        if not any(needs[:3]):
+        if not any(needs[:3]) and not needs[5]:
             return (None,) * 6
         q, k, v, out, lse = ctx.saved_tensors
         if grad_out.stride(-1) != 1 or grad_out.stride(-2) < grad_out.shape[-1] or (grad_out.dim() == 3 and grad_out.stride(0) < 1):
             grad_out = grad_out.contiguous()                       # e.g. out.sum().backward() hands in an expanded scalar
-        grads = ops.attention_csr_bwd(a.fwd, a.tpattern, a.perm32(), q, k, v, out, lse, grad_out, scale=ctx.scale, bias=ctx.bias,
-                                      need=tuple(needs[:3]))
-        return (*grads, None, None, None)
+        grads, grad_bias = (None, None, None), None
+        if any(needs[:3]):
+            grads = ops.attention_csr_bwd(a.fwd, a.tpattern, a.perm32(), q, k, v, out, lse, grad_out, scale=ctx.scale, bias=ctx.bias,
+                                          need=tuple(needs[:3]))
+        if needs[5]:
+            from . import attn_csr_dbias
+            grad_bias = _bias_grad(attn_csr_dbias.attention_csr_dbias(a.fwd, q, k, v, out, lse, grad_out, ctx.scale, ctx.bias), ctx.bias)
+        return (*grads, None, None, grad_bias)
 
 
 def _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward=False):
@@ -275,7 +301,7 @@ def _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward=False):
     return _FusedSparseAttention.apply(q, k, v, a, float(scale), bias)
 
 
-def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=False, fused_backward=False):
+def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=False, fused_backward=False, bias_grad=False):
     """Attention on A's pattern: row r attends to the columns A stores in row r.
 
         scores = sddmm(a, q * scale, k)        # [nnz]   <q_r, k_c> for every stored (r, c)
@@ -286,7 +312,7 @@ def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=F
     or float64), unit column stride.  scale defaults to D ** -0.5 and is applied to q by a torch multiply.  Differentiable in
     q, k and v; a row of A without entries gives a zero row.
     bias: a tensor of a's dtype over A's entries ([nnz]), added to the scores by a torch add before the softmax; -Inf = a
-    masked entry.  It is a constant: one that requires a gradient is refused.
+    masked entry.  It is a constant: one that requires a gradient is refused -- unless bias_grad=True (below).
     fused=True (float32 only; off by default): the forward is ONE launch for all heads (ops.attention_csr: online softmax in
     fp32, the scale applied to the scores by the kernel's fma, neither scores nor P written); q, k, v may then be [H, M, D] /
     [H, K, D] / [H, K, Dv] with any head and row strides and out is [H, M, Dv]; bias [nnz] or [H, nnz]; acc is not read: the
@@ -298,16 +324,23 @@ def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=F
     are saved; the backward is ONE ops.attention_csr_bwd call, at most two launches for all heads (a row pass for dq, a column
     pass on A^T's pattern for dk and dv), nothing recomputed through memory, work for inputs that need no gradient skipped.
     Its gradients are not the chain's bits -- P comes from the stored lse and the softmax backward's row term from
-    <grad_out, out> -- and are held to derived tolerances (include/mispmm_attn_csr_bwd.h, NUMERICS)."""
+    <grad_out, out> -- and are held to derived tolerances (include/mispmm_attn_csr_bwd.h, NUMERICS).
+    bias_grad=True (off by default): a bias that requires a gradient is accepted and gets one; the gradients of q, k and v are
+    the same bits as with a constant bias.  Unfused: the torch add differentiates it.  fused=True: the recomputing backward's
+    ds of each head (ops.softmax_csr_bwd) IS that head's bias gradient and is returned.  fused_backward=True: one launch more
+    for all heads (attn_csr_dbias.attention_csr_dbias, include/mispmm_attn_csr_dbias.h), made only where the bias needs a
+    gradient; ops.attention_csr_bwd is skipped where nothing else does.  A bias [nnz] shared by H heads gets the heads' sum (one
+    torch.sum over the per-head result)."""
     if fused_backward and not fused:
         raise ValueError("fused_backward=True needs fused=True: the fused backward reads the fused forward's out and lse")
     ops._require_gpu(a.fwd.row_ptrs, q, k, v, bias)
     if bias is not None:
-        if bias.requires_grad:
+        if bias.requires_grad and not bias_grad:
             raise ValueError("bias is a constant: it gets no gradient and must not require one")
         if bias.dtype != a.fwd.data.dtype:
             raise ValueError(f"bias must be {a.fwd.data.dtype}, like the matrix")
-        bias = bias.detach()
+        if not bias.requires_grad:
+            bias = bias.detach()
     if fused:
         return _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward)
     dtype = a.fwd.data.dtype
@@ -670,11 +703,13 @@ def spmm_bf16(a, values, b, out_dtype=torch.bfloat16, acc="fast", sddmm="f32"):
 # ---- fused attention on a CSR pattern with the activations in bf16 (attn_csr_bf16.attention_csr_bf16)
 class _SparseAttentionBf16(torch.autograd.Function):
     """The forward in one launch for all heads, reading bf16 (fp32 out and lse); q, k, v, out and lse are saved.  The backward
-    is ops.attention_csr_bwd on the widened q, k, v with the saved fp32 out and lse, every gradient rounded once."""
+    is ops.attention_csr_bwd on the widened q, k, v with the saved fp32 out and lse, every gradient rounded once.  A bias that
+    requires a gradient gets it in fp32 by attn_csr_dbias.attention_csr_dbias on the same widened operands."""
     @staticmethod
     def forward(ctx, q, k, v, a, scale, bias, out_bf16):
         from . import attn_csr_bf16
         q, k, v = q.detach(), k.detach(), v.detach()
+        bias = None if bias is None else bias.detach()
         out, lse = attn_csr_bf16.attention_csr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, bias=bias, return_lse=True)
         ctx.a, ctx.scale, ctx.bias = a, scale, bias
         ctx.save_for_backward(q, k, v, out, lse)
@@ -684,7 +719,7 @@ class _SparseAttentionBf16(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         a, needs = ctx.a, ctx.needs_input_grad
-        if not any(needs[:3]):
+        if not any(needs[:3]) and not needs[5]:
             return (None,) * 7
         q, k, v, out, lse = ctx.saved_tensors
         if grad_out.dtype == torch.bfloat16:
@@ -692,19 +727,26 @@ class _SparseAttentionBf16(torch.autograd.Function):
         elif grad_out.stride(-1) != 1 or grad_out.stride(-2) < grad_out.shape[-1] or (grad_out.dim() == 3 and grad_out.stride(0) < 1):
             grad_out = grad_out.contiguous()                       # e.g. out.sum().backward() hands in an expanded scalar
         qf, kf, vf = (ops.bf16_to_f32(_bits(t)) for t in (q, k, v))
-        grads = ops.attention_csr_bwd(a.fwd, a.tpattern, a.perm32(), qf, kf, vf, out, lse, grad_out, scale=ctx.scale, bias=ctx.bias,
-                                      need=tuple(needs[:3]))
-        return (*(None if g is None else ops.f32_to_bf16(g).view(torch.bfloat16) for g in grads), None, None, None, None)
+        grads, grad_bias = (None, None, None), None
+        if any(needs[:3]):
+            grads = ops.attention_csr_bwd(a.fwd, a.tpattern, a.perm32(), qf, kf, vf, out, lse, grad_out, scale=ctx.scale, bias=ctx.bias,
+                                          need=tuple(needs[:3]))
+        if needs[5]:
+            from . import attn_csr_dbias
+            grad_bias = _bias_grad(attn_csr_dbias.attention_csr_dbias(a.fwd, qf, kf, vf, out, lse, grad_out, ctx.scale, ctx.bias), ctx.bias)
+        return (*(None if g is None else ops.f32_to_bf16(g).view(torch.bfloat16) for g in grads), None, None, grad_bias, None)
 
 
 class _SparseAttentionBf16FusedBwd(torch.autograd.Function):
     """The same forward with a bfloat16 result; the backward is ONE attn_csr_bf16.attention_csr_bf16_bwd call on the saved q, k,
     v, fp32 out and lse and the bfloat16 grad_out: at most two launches for all heads, nothing widened or narrowed through
-    memory, `need` set from the inputs that require a gradient."""
+    memory, `need` set from the inputs that require a gradient.  A bias that requires a gradient gets it in fp32 by one launch
+    more that reads bf16 itself (attn_csr_dbias.attention_csr_dbias_bf16)."""
     @staticmethod
     def forward(ctx, q, k, v, a, scale, bias):
         from . import attn_csr_bf16
         q, k, v = q.detach(), k.detach(), v.detach()
+        bias = None if bias is None else bias.detach()
         out, lse = attn_csr_bf16.attention_csr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, bias=bias, return_lse=True)
         ctx.a, ctx.scale, ctx.bias = a, scale, bias
         ctx.save_for_backward(q, k, v, out, lse)
@@ -715,24 +757,30 @@ class _SparseAttentionBf16FusedBwd(torch.autograd.Function):
     def backward(ctx, grad_out):
         from . import attn_csr_bf16
         a, needs = ctx.a, ctx.needs_input_grad
-        if not any(needs[:3]):
+        if not any(needs[:3]) and not needs[5]:
             return (None,) * 6
         q, k, v, out, lse = ctx.saved_tensors
         if grad_out.stride(-1) != 1 or grad_out.stride(-2) < grad_out.shape[-1] or (grad_out.dim() == 3 and grad_out.stride(0) < 1):
             grad_out = grad_out.contiguous()                       # e.g. out.sum().backward() hands in an expanded scalar
-        grads = attn_csr_bf16.attention_csr_bf16_bwd(a.fwd, a.tpattern, a.perm32(), _bits(q), _bits(k), _bits(v), out, lse, _bits(grad_out),
-                                                     scale=ctx.scale, bias=ctx.bias, need=tuple(needs[:3]), grads_bf16=True)
-        return (*(None if g is None else g.view(torch.bfloat16) for g in grads), None, None, None)
+        grads, grad_bias = (None, None, None), None
+        if any(needs[:3]):
+            grads = attn_csr_bf16.attention_csr_bf16_bwd(a.fwd, a.tpattern, a.perm32(), _bits(q), _bits(k), _bits(v), out, lse, _bits(grad_out),
+                                                         scale=ctx.scale, bias=ctx.bias, need=tuple(needs[:3]), grads_bf16=True)
+        if needs[5]:
+            from . import attn_csr_dbias
+            grad_bias = _bias_grad(attn_csr_dbias.attention_csr_dbias_bf16(a.fwd, _bits(q), _bits(k), _bits(v), out, lse, _bits(grad_out), ctx.scale,
+                                                                           ctx.bias), ctx.bias)
+        return (*(None if g is None else g.view(torch.bfloat16) for g in grads), None, None, grad_bias)
 
 
-def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfloat16, fused_backward=False):
+def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfloat16, fused_backward=False, bias_grad=False):
     """Attention on A's pattern with the activations in bfloat16: row r attends to the columns A stores in row r, one launch
     for all heads (attn_csr_bf16.attention_csr_bf16: fp32 arithmetic on the exactly widened operands, online softmax, neither
     scores nor weights written, no fp32 copy of q, k or v).
     a: a float32 TrainableCSR [M x K] (its values are not read); q: [M, D], k: [K, D], v: [K, Dv] torch.bfloat16 device
     tensors, or [H, ...] with any head and row strides and unit column stride; D and Dv from 1 to 256.  scale defaults to
     D ** -0.5.  bias: a float32 tensor over A's entries, [nnz] or [H, nnz], added to the scaled scores, -Inf = a masked entry;
-    a constant: one that requires a gradient is refused.  out_dtype: torch.bfloat16 (the default) or torch.float32.  The
+    a constant: one that requires a gradient is refused -- unless bias_grad=True (below).  out_dtype: torch.bfloat16 (the default) or torch.float32.  The
     kernel is always asked for its fp32 out and lse, which the backward reads; a bfloat16 result is ops.f32_to_bf16 of that
     out -- ONE extra elementwise launch, the same single rounding to nearest even the kernel's own bf16 store makes.
     Differentiable in q, k and v.  The backward is DEFINED as ops.attention_csr_bwd (at most two launches for all heads) on
@@ -744,7 +792,12 @@ def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfl
     launches for all heads that read bf16 themselves and round each gradient once at the store; a grad_out that is not
     unit-stride with rows that do not overlap is made contiguous first.  On 16-byte lanes its gradients are not the default
     backward's bits (a lane's dot-product chain covers 8 columns against 4) and are held to the same derived tolerances.
-    Not built: a fused backward for a float32 grad_out, which is why the keyword is refused with out_dtype=torch.float32."""
+    Not built: a fused backward for a float32 grad_out, which is why the keyword is refused with out_dtype=torch.float32.
+    bias_grad=True (off by default): a bias that requires a gradient is accepted and gets one, in float32, by one launch more
+    for all heads, made only then: attn_csr_dbias.attention_csr_dbias on the widened operands the default backward holds, or
+    with fused_backward=True attn_csr_dbias.attention_csr_dbias_bf16, which reads bf16 itself.  The backward call proper is
+    skipped where q, k and v need nothing; their gradients are the same bits as with a constant bias.  A bias [nnz] shared by
+    H heads gets the heads' sum (one torch.sum over the per-head result)."""
     if fused_backward and out_dtype == torch.float32:
         raise ValueError("fused_backward=True needs out_dtype=torch.bfloat16: with a float32 out, grad_out would be float32, and the fused "
                          "bf16 backward reads a bfloat16 grad_out")
@@ -763,11 +816,12 @@ def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfl
     if q.shape[-1] != k.shape[-1]:
         raise ValueError(f"q and k must have the same number of columns, not {q.shape[-1]} and {k.shape[-1]}")
     if bias is not None:
-        if bias.requires_grad:
+        if bias.requires_grad and not bias_grad:
             raise ValueError("bias is a constant: it gets no gradient and must not require one")
         if bias.dtype != torch.float32:
             raise ValueError(f"bias must be torch.float32, not {bias.dtype}")
-        bias = bias.detach()
+        if not bias.requires_grad:
+            bias = bias.detach()
     if scale is None:
         scale = q.shape[-1] ** -0.5
     if fused_backward:
