@@ -1,11 +1,12 @@
 // libmispmm_attn_csr_bf16.so: fused attention on a CSR pattern with Q, K and V in bf16 (include/mispmm_attn_csr_bf16.h) --
 // scores, row softmax and the product with V in ONE launch for all heads, fp32 arithmetic on the exactly widened operands;
 // out in fp32, or that fp32 result rounded once to bf16 (a wave-uniform branch of the store: no instances of its own).
-// The kernel is attn_csr/attn_csr_fwd.hpp's over ElemBf16 (V8: 16-byte lanes, or V1); what stands here is the entry point:
-// its refusals, the choice of the lane width and the parameter block.
+// The kernel is attn_csr/attn_csr_fwd.hpp's over ElemBf16 (V8: 16-byte lanes, or V1) and the entry point is
+// attn_csr/attn_csr_entry.hpp's fwd_entry over the same policy (its refusals, the choice of the lane width and the parameter
+// block); what stands here is the export, its name and its tag.
 // The sources lie outside csrc/, fused/, rows_bf16/ and attn_csr/: the census tests hold those directories and their
 // libraries to their records.
-#include "../attn_csr/attn_csr_fwd.hpp"
+#include "../attn_csr/attn_csr_entry.hpp"
 #include "mispmm_attn_csr_bf16.h"
 
 using namespace mispmm;
@@ -15,47 +16,7 @@ extern "C" int mispmm_attn_csr_bf16(mispmm_stream_t stream, uint32_t H, uint32_t
                                     uint64_t k_head_stride, uint32_t ldk, uint32_t D, const uint16_t *V, uint64_t v_head_stride, uint32_t ldv,
                                     uint32_t Dv, float scale, const float *bias, uint64_t bias_head_stride, void *out,
                                     uint64_t out_head_stride, uint32_t ldo, int out_bf16, float *lse) {
-    if (const int st = refuse_shape("attn_csr_bf16", D, Dv, scale); st != MISPMM_OK) return st;
-    if (H == 0 || M == 0) return MISPMM_OK;
-    if (!rowPtrs || !Q || !Kmat || !V || !out || (nnz != 0 && !colIdxs))
-        return fail(MISPMM_ERR_INVALID_ARG, "attn_csr_bf16: rowPtrs, colIdxs, Q, K, V or out is null");
-    if (ldq < D || ldk < D || ldv < Dv || ldo < Dv)
-        return fail(MISPMM_ERR_INVALID_ARG, "attn_csr_bf16: leading dimension smaller than the width (D=%u ldq=%u ldk=%u, Dv=%u ldv=%u ldo=%u)",
-                    D, ldq, ldk, Dv, ldv, ldo);
-    // a raw buffer descriptor spans less than 2 GiB and bit 31 of an offset marks a dropped load: bytes of the element type
-    const uint64_t o_elem = out_bf16 ? 2u : 4u;
-    const uint64_t qs = span(M, ldq, D) * 2u, ks = span(K, ldk, D) * 2u, vs = span(K, ldv, Dv) * 2u, os = span(M, ldo, Dv) * o_elem;
-    const uint64_t bs = bias ? static_cast<uint64_t>(nnz) * 4u : 0u;
-    if (qs > 0x7FFFFFFFull || ks > 0x7FFFFFFFull || vs > 0x7FFFFFFFull || os > 0x7FFFFFFFull || bs > 0x7FFFFFFFull)
-        return fail(MISPMM_ERR_UNSUPPORTED,
-                    "attn_csr_bf16: Q, K, V, out or bias of one head spans 2 GiB or more (%llu, %llu, %llu, %llu, %llu bytes)",
-                    static_cast<unsigned long long>(qs), static_cast<unsigned long long>(ks), static_cast<unsigned long long>(vs),
-                    static_cast<unsigned long long>(os), static_cast<unsigned long long>(bs));
-    const bool wide = D % 8 == 0 && Dv % 8 == 0 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 && q_head_stride % 8 == 0 &&
-                      k_head_stride % 8 == 0 && v_head_stride % 8 == 0 && out_head_stride % 8 == 0 && aligned16(Q) && aligned16(Kmat) &&
-                      aligned16(V) && aligned16(out);
-    const int vec = wide ? 8 : 1;
-    const uint32_t width = D > Dv ? D : Dv;
-    const int g = pick_group(width, vec);
-    if (const int st = refuse_grid("attn_csr_bf16", M, H, g); st != MISPMM_OK) return st;
-    if (!aligned2(Q) || !aligned2(Kmat) || !aligned2(V) || (out_bf16 && !aligned2(out)))
-        return fail(MISPMM_ERR_INVALID_ARG, "attn_csr_bf16: Q, K, V and a bf16 out must be 2-byte aligned");
-    FwdCall<ElemBf16> c{};
-    c.stream = as_stream(stream);
-    c.H = H;
-    c.rowPtrs = rowPtrs, c.colIdxs = colIdxs;
-    c.Q = Q, c.K = Kmat, c.V = V, c.bias = bias, c.out = out, c.lse = lse;
-    FwdParams<ElemBf16> &p = c.p;
-    p.M = M, p.D = D, p.Dv = Dv;
-    p.ldq = ldq * 2u, p.ldk = ldk * 2u, p.ldv = ldv * 2u, p.ldo = ldo;
-    p.q_bytes = static_cast<uint32_t>(qs), p.k_bytes = static_cast<uint32_t>(ks), p.v_bytes = static_cast<uint32_t>(vs);
-    p.bias_bytes = static_cast<uint32_t>(bs);
-    p.narrow = out_bf16 ? 1u : 0u;
-    p.scale = scale;
-    p.q_head = q_head_stride, p.k_head = k_head_stride, p.v_head = v_head_stride, p.o_head = out_head_stride, p.bias_head = bias_head_stride;
-    ElemBf16::with_instance(vec, g, width, [&](auto gr, auto v, auto ch) {
-        launch_attn_csr<ElemBf16, decltype(gr)::value, decltype(v)::value, decltype(ch)::value>(c, "attn_csr_bf16<G%d,V%d,C%d>");
-    });
-    MISPMM_LAUNCH_CHECK();
-    return MISPMM_OK;
+    return fwd_entry<ElemBf16>("attn_csr_bf16", "attn_csr_bf16<G%d,V%d,C%d>", stream, H, M, K, nnz, rowPtrs, colIdxs, Q, q_head_stride, ldq, Kmat,
+                               k_head_stride, ldk, D, V, v_head_stride, ldv, Dv, scale, bias, bias_head_stride, out, out_head_stride, ldo, out_bf16,
+                               lse);
 }

@@ -40,9 +40,10 @@ Both gradients come back in bfloat16.  The CSR product with fp32 values and the 
                                                        # ([nnz] or [H, nnz]): b.grad by one more launch for all heads
                                                        # (attn_csr_dbias.attention_csr_dbias); every other path takes the keyword too
 
-Not built: COO / ELL patterns, bf16 for SDDMM / softmax on a CSR pattern, a head-summed bias gradient from the kernel (a bias
-shared by the heads gets the per-head result summed by torch), the column-compacted block layouts (their tiles are built on the
-host from the values), a device kernel for the blocks[perm] transpose."""
+Not built: COO / ELL patterns, bf16 for the softmax on a CSR pattern (SDDMM has it: sddmm_bf16.sddmm_csr_bf16, which
+spmm_bf16(sddmm="bf16") uses), a head-summed bias gradient from the kernel (a bias shared by the heads gets the per-head result
+summed by torch), the column-compacted block layouts (their tiles are built on the host from the values), a device kernel for
+the blocks[perm] transpose."""
 import dataclasses
 from dataclasses import dataclass
 
@@ -192,6 +193,55 @@ def _bias_grad(per_head, bias):
     return per_head.reshape(bias.shape)
 
 
+# ---- what the fused attention on a CSR pattern, float32 and bfloat16, checks and does alike
+def _of_dtype(t, dtype, what, like=None):
+    if t.dtype != dtype:
+        raise ValueError(f"{what} must be {dtype}" + (like or f", not {t.dtype}"))
+
+
+def _check_fused_qkv(a, q, k, v, dtype, like=None):
+    """q, k and v of a fused call: all 2-D or all [H, ...] of `dtype`, the rows of A's pattern, q's heads, k of q's width."""
+    if {t.dim() for t in (q, k, v)} not in ({2}, {3}):
+        raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    for t, rows, what in ((q, a.fwd.num_rows, "q"), (k, a.fwd.num_cols, "k"), (v, a.fwd.num_cols, "v")):
+        _of_dtype(t, dtype, what, like)
+        if t.shape[-2] != rows or t.shape[:-2] != q.shape[:-2]:
+            raise ValueError(f"{what} must be [{rows}, N] or [H, {rows}, N] with q's H, not {tuple(t.shape)}")
+    if q.shape[-1] != k.shape[-1]:
+        raise ValueError(f"q and k must have the same number of columns, not {q.shape[-1]} and {k.shape[-1]}")
+
+
+def _bias_gate(bias, bias_grad, dtype, like=None):
+    """A bias is a constant of `dtype` -- one that requires a gradient is refused -- unless bias_grad; a constant is detached."""
+    if bias is None:
+        return None
+    if bias.requires_grad and not bias_grad:
+        raise ValueError("bias is a constant: it gets no gradient and must not require one")
+    _of_dtype(bias, dtype, "bias", like)
+    return bias if bias.requires_grad else bias.detach()
+
+
+def _dense_grad(grad_out):
+    """grad_out as the library reads it: unit column stride, rows and heads that do not overlap -- else a contiguous copy
+    (out.sum().backward() hands in an expanded scalar)."""
+    if grad_out.stride(-1) != 1 or grad_out.stride(-2) < grad_out.shape[-1] or (grad_out.dim() == 3 and grad_out.stride(0) < 1):
+        return grad_out.contiguous()
+    return grad_out
+
+
+def _lse_backward(ctx, bwd, dbias, q, k, v, out, lse, grad_out, **kw):
+    """The tail of a backward that reads the saved out and lse: ONE `bwd` call if any of q, k, v needs a gradient, with `need`
+    set from them (kw: further keywords of `bwd`), and one `dbias` call if the bias does.  Returns ((dq, dk, dv), grad_bias),
+    None where not asked for."""
+    a, needs = ctx.a, ctx.needs_input_grad
+    grads, grad_bias = (None, None, None), None
+    if any(needs[:3]):
+        grads = bwd(a.fwd, a.tpattern, a.perm32(), q, k, v, out, lse, grad_out, scale=ctx.scale, bias=ctx.bias, need=tuple(needs[:3]), **kw)
+    if needs[5]:
+        grad_bias = _bias_grad(dbias(a.fwd, q, k, v, out, lse, grad_out, ctx.scale, ctx.bias), ctx.bias)
+    return grads, grad_bias
+
+
 class _FusedSparseAttention(torch.autograd.Function):
     """The forward in one launch for all heads (ops.attention_csr).  q, k, v are saved and the weights are not: the backward
     recomputes the scores and P head by head with the FAST kernels of the four-launch forward and runs its gradient chain, so
@@ -219,8 +269,7 @@ class _FusedSparseAttention(torch.autograd.Function):
         for h in heads:
             qh, kh, vh, gh = (t if h is None else t[h] for t in (q, k, v, grad_out))
             bh = bias if bias is None or bias.dim() == 1 else bias[h]
-            if gh.stride(1) != 1 or gh.stride(0) < gh.shape[1]:      # e.g. out.sum().backward() hands in an expanded scalar
-                gh = gh.contiguous()
+            gh = _dense_grad(gh)
             qs = qh * scale
             s = ops.sddmm_csr(a.fwd, qs, kh, acc="fast")
             p = ops.softmax_csr(a.fwd, s if bh is None else s + bh, acc="fast")
@@ -259,19 +308,11 @@ class _FusedSparseAttentionFusedBwd(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        a, needs = ctx.a, ctx.needs_input_grad
+        from . import attn_csr_dbias
+        needs = ctx.needs_input_grad
         if not any(needs[:3]) and not needs[5]:
             return (None,) * 6
-        q, k, v, out, lse = ctx.saved_tensors
-        if grad_out.stride(-1) != 1 or grad_out.stride(-2) < grad_out.shape[-1] or (grad_out.dim() == 3 and grad_out.stride(0) < 1):
-            grad_out = grad_out.contiguous()                       # e.g. out.sum().backward() hands in an expanded scalar
-        grads, grad_bias = (None, None, None), None
-        if any(needs[:3]):
-            grads = ops.attention_csr_bwd(a.fwd, a.tpattern, a.perm32(), q, k, v, out, lse, grad_out, scale=ctx.scale, bias=ctx.bias,
-                                          need=tuple(needs[:3]))
-        if needs[5]:
-            from . import attn_csr_dbias
-            grad_bias = _bias_grad(attn_csr_dbias.attention_csr_dbias(a.fwd, q, k, v, out, lse, grad_out, ctx.scale, ctx.bias), ctx.bias)
+        grads, grad_bias = _lse_backward(ctx, ops.attention_csr_bwd, attn_csr_dbias.attention_csr_dbias, *ctx.saved_tensors, _dense_grad(grad_out))
         return (*grads, None, None, grad_bias)
 
 
@@ -279,18 +320,10 @@ def _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward=False):
     dtype = a.fwd.data.dtype
     if dtype != torch.float32:
         raise ValueError("fused=True takes a float32 matrix: the fused kernel has one arithmetic, fp32")
-    dims = {t.dim() for t in (q, k, v)}
-    if dims not in ({2}, {3}):
-        raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
-    for t, rows, what in ((q, a.fwd.num_rows, "q"), (k, a.fwd.num_cols, "k"), (v, a.fwd.num_cols, "v")):
-        if t.dtype != dtype:
-            raise ValueError(f"{what} must be {dtype}, like the matrix")
-        if t.shape[-2] != rows or t.shape[:-2] != q.shape[:-2]:
-            raise ValueError(f"{what} must be [{rows}, N] or [H, {rows}, N] with q's H, not {tuple(t.shape)}")
+    _check_fused_qkv(a, q, k, v, dtype, ", like the matrix")
+    for t, what in ((q, "q"), (k, "k"), (v, "v")):
         if t.shape[-1] > 1 and t.stride(-1) != 1:
             raise ValueError(f"{what} must have unit column stride")
-    if q.shape[-1] != k.shape[-1]:
-        raise ValueError(f"q and k must have the same number of columns, not {q.shape[-1]} and {k.shape[-1]}")
     heads = q.shape[0] if q.dim() == 3 else 1
     if bias is not None and tuple(bias.shape) not in ((a.fwd.nnz,), (heads, a.fwd.nnz)):
         raise ValueError(f"bias must be [{a.fwd.nnz}] or [{heads}, {a.fwd.nnz}], not {tuple(bias.shape)}")
@@ -334,13 +367,7 @@ def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=F
     if fused_backward and not fused:
         raise ValueError("fused_backward=True needs fused=True: the fused backward reads the fused forward's out and lse")
     ops._require_gpu(a.fwd.row_ptrs, q, k, v, bias)
-    if bias is not None:
-        if bias.requires_grad and not bias_grad:
-            raise ValueError("bias is a constant: it gets no gradient and must not require one")
-        if bias.dtype != a.fwd.data.dtype:
-            raise ValueError(f"bias must be {a.fwd.data.dtype}, like the matrix")
-        if not bias.requires_grad:
-            bias = bias.detach()
+    bias = _bias_gate(bias, bias_grad, a.fwd.data.dtype, ", like the matrix")
     if fused:
         return _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward)
     dtype = a.fwd.data.dtype
@@ -701,39 +728,41 @@ def spmm_bf16(a, values, b, out_dtype=torch.bfloat16, acc="fast", sddmm="f32"):
 
 
 # ---- fused attention on a CSR pattern with the activations in bf16 (attn_csr_bf16.attention_csr_bf16)
+def _bf16_forward(ctx, q, k, v, a, scale, bias):
+    """The forward of both Functions below: one launch for all heads, reading bf16; q, k, v, the fp32 out and lse are saved and
+    the fp32 out returned."""
+    from . import attn_csr_bf16
+    q, k, v = q.detach(), k.detach(), v.detach()
+    bias = None if bias is None else bias.detach()
+    out, lse = attn_csr_bf16.attention_csr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, bias=bias, return_lse=True)
+    ctx.a, ctx.scale, ctx.bias = a, scale, bias
+    ctx.save_for_backward(q, k, v, out, lse)
+    return out
+
+
 class _SparseAttentionBf16(torch.autograd.Function):
     """The forward in one launch for all heads, reading bf16 (fp32 out and lse); q, k, v, out and lse are saved.  The backward
     is ops.attention_csr_bwd on the widened q, k, v with the saved fp32 out and lse, every gradient rounded once.  A bias that
     requires a gradient gets it in fp32 by attn_csr_dbias.attention_csr_dbias on the same widened operands."""
     @staticmethod
     def forward(ctx, q, k, v, a, scale, bias, out_bf16):
-        from . import attn_csr_bf16
-        q, k, v = q.detach(), k.detach(), v.detach()
-        bias = None if bias is None else bias.detach()
-        out, lse = attn_csr_bf16.attention_csr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, bias=bias, return_lse=True)
-        ctx.a, ctx.scale, ctx.bias = a, scale, bias
-        ctx.save_for_backward(q, k, v, out, lse)
+        out = _bf16_forward(ctx, q, k, v, a, scale, bias)
         return ops.f32_to_bf16(out).view(torch.bfloat16) if out_bf16 else out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        a, needs = ctx.a, ctx.needs_input_grad
+        from . import attn_csr_dbias
+        needs = ctx.needs_input_grad
         if not any(needs[:3]) and not needs[5]:
             return (None,) * 7
         q, k, v, out, lse = ctx.saved_tensors
         if grad_out.dtype == torch.bfloat16:
             grad_out = ops.bf16_to_f32(_bits(grad_out))            # exact; a view that is not contiguous is copied there
-        elif grad_out.stride(-1) != 1 or grad_out.stride(-2) < grad_out.shape[-1] or (grad_out.dim() == 3 and grad_out.stride(0) < 1):
-            grad_out = grad_out.contiguous()                       # e.g. out.sum().backward() hands in an expanded scalar
+        else:
+            grad_out = _dense_grad(grad_out)
         qf, kf, vf = (ops.bf16_to_f32(_bits(t)) for t in (q, k, v))
-        grads, grad_bias = (None, None, None), None
-        if any(needs[:3]):
-            grads = ops.attention_csr_bwd(a.fwd, a.tpattern, a.perm32(), qf, kf, vf, out, lse, grad_out, scale=ctx.scale, bias=ctx.bias,
-                                          need=tuple(needs[:3]))
-        if needs[5]:
-            from . import attn_csr_dbias
-            grad_bias = _bias_grad(attn_csr_dbias.attention_csr_dbias(a.fwd, qf, kf, vf, out, lse, grad_out, ctx.scale, ctx.bias), ctx.bias)
+        grads, grad_bias = _lse_backward(ctx, ops.attention_csr_bwd, attn_csr_dbias.attention_csr_dbias, qf, kf, vf, out, lse, grad_out)
         return (*(None if g is None else ops.f32_to_bf16(g).view(torch.bfloat16) for g in grads), None, None, grad_bias, None)
 
 
@@ -744,32 +773,18 @@ class _SparseAttentionBf16FusedBwd(torch.autograd.Function):
     more that reads bf16 itself (attn_csr_dbias.attention_csr_dbias_bf16)."""
     @staticmethod
     def forward(ctx, q, k, v, a, scale, bias):
-        from . import attn_csr_bf16
-        q, k, v = q.detach(), k.detach(), v.detach()
-        bias = None if bias is None else bias.detach()
-        out, lse = attn_csr_bf16.attention_csr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, bias=bias, return_lse=True)
-        ctx.a, ctx.scale, ctx.bias = a, scale, bias
-        ctx.save_for_backward(q, k, v, out, lse)
-        return ops.f32_to_bf16(out).view(torch.bfloat16)
+        return ops.f32_to_bf16(_bf16_forward(ctx, q, k, v, a, scale, bias)).view(torch.bfloat16)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        from . import attn_csr_bf16
-        a, needs = ctx.a, ctx.needs_input_grad
+        from . import attn_csr_bf16, attn_csr_dbias
+        needs = ctx.needs_input_grad
         if not any(needs[:3]) and not needs[5]:
             return (None,) * 6
         q, k, v, out, lse = ctx.saved_tensors
-        if grad_out.stride(-1) != 1 or grad_out.stride(-2) < grad_out.shape[-1] or (grad_out.dim() == 3 and grad_out.stride(0) < 1):
-            grad_out = grad_out.contiguous()                       # e.g. out.sum().backward() hands in an expanded scalar
-        grads, grad_bias = (None, None, None), None
-        if any(needs[:3]):
-            grads = attn_csr_bf16.attention_csr_bf16_bwd(a.fwd, a.tpattern, a.perm32(), _bits(q), _bits(k), _bits(v), out, lse, _bits(grad_out),
-                                                         scale=ctx.scale, bias=ctx.bias, need=tuple(needs[:3]), grads_bf16=True)
-        if needs[5]:
-            from . import attn_csr_dbias
-            grad_bias = _bias_grad(attn_csr_dbias.attention_csr_dbias_bf16(a.fwd, _bits(q), _bits(k), _bits(v), out, lse, _bits(grad_out), ctx.scale,
-                                                                           ctx.bias), ctx.bias)
+        grads, grad_bias = _lse_backward(ctx, attn_csr_bf16.attention_csr_bf16_bwd, attn_csr_dbias.attention_csr_dbias_bf16, _bits(q), _bits(k),
+                                         _bits(v), out, lse, _bits(_dense_grad(grad_out)), grads_bf16=True)
         return (*(None if g is None else g.view(torch.bfloat16) for g in grads), None, None, grad_bias)
 
 
@@ -805,23 +820,8 @@ def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfl
     out_bf16 = _check_out_dtype(out_dtype)
     if a.fwd.data.dtype != torch.float32:
         raise ValueError("sparse_attention_bf16 takes a float32 matrix")
-    dims = {t.dim() for t in (q, k, v)}
-    if dims not in ({2}, {3}):
-        raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
-    for t, rows, what in ((q, a.fwd.num_rows, "q"), (k, a.fwd.num_cols, "k"), (v, a.fwd.num_cols, "v")):
-        if t.dtype != torch.bfloat16:
-            raise ValueError(f"{what} must be torch.bfloat16, not {t.dtype}")
-        if t.shape[-2] != rows or t.shape[:-2] != q.shape[:-2]:
-            raise ValueError(f"{what} must be [{rows}, N] or [H, {rows}, N] with q's H, not {tuple(t.shape)}")
-    if q.shape[-1] != k.shape[-1]:
-        raise ValueError(f"q and k must have the same number of columns, not {q.shape[-1]} and {k.shape[-1]}")
-    if bias is not None:
-        if bias.requires_grad and not bias_grad:
-            raise ValueError("bias is a constant: it gets no gradient and must not require one")
-        if bias.dtype != torch.float32:
-            raise ValueError(f"bias must be torch.float32, not {bias.dtype}")
-        if not bias.requires_grad:
-            bias = bias.detach()
+    _check_fused_qkv(a, q, k, v, torch.bfloat16)
+    bias = _bias_gate(bias, bias_grad, torch.float32)
     if scale is None:
         scale = q.shape[-1] ** -0.5
     if fused_backward:

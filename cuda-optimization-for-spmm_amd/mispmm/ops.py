@@ -674,50 +674,6 @@ def softmax_csr_bwd(a, p, dp, out=None, acc="reference", stream=None):
 ATTN_CSR_MAX_WIDTH = 256     # D and Dv of the fused CSR attention kernel: 1 up to this (mispmm_attn_csr.h)
 
 
-def _attn_csr_operand(t, rows, heads, what):
-    """(t as [H, rows, width], row stride, head stride) of a float32 operand given as [rows, width] or [H, rows, width]."""
-    if t.dtype != torch.float32 or t.dim() not in (2, 3):
-        raise ValueError(f"{what} must be a float32 tensor, [{rows}, width] or [H, {rows}, width], not {t.dtype} {tuple(t.shape)}")
-    if t.dim() == 2:
-        t = t.unsqueeze(0)
-    if t.shape[1] != rows or (heads is not None and t.shape[0] != heads):
-        raise ValueError(f"{what} must be [{rows}, width] or [{'H' if heads is None else heads}, {rows}, width], not {tuple(t.shape)}")
-    width = t.shape[2]
-    if width > 1 and t.stride(2) != 1:
-        raise ValueError(f"{what} must have unit column stride")
-    if width == 0 or width > ATTN_CSR_MAX_WIDTH:
-        raise ValueError(f"the fused CSR attention kernel takes widths from 1 to {ATTN_CSR_MAX_WIDTH}: {what} has {width} columns")
-    ld = t.stride(1) if rows > 1 else max(width, t.stride(1))
-    if ld < width or any(s < 0 for s in t.stride()):
-        raise ValueError(f"{what} must not overlap its own rows (row stride {ld} < {width} columns), e.g. an expanded tensor")
-    return t, ld, (t.stride(0) if t.shape[0] > 1 else 0)
-
-
-def _attn_csr_qkv(a, q, k, v):
-    """_attn_csr_operand of q, k and v for the pattern a: k and v of q's heads, k of q's width."""
-    q3 = _attn_csr_operand(q, a.num_rows, None, "q")
-    heads = q3[0].shape[0]
-    k3 = _attn_csr_operand(k, a.num_cols, heads, "k")
-    v3 = _attn_csr_operand(v, a.num_cols, heads, "v")
-    if k3[0].shape[2] != q3[0].shape[2]:
-        raise ValueError(f"q and k must have the same number of columns, not {q3[0].shape[2]} and {k3[0].shape[2]}")
-    return q3, k3, v3
-
-
-def _attn_csr_bias_head(a, bias, heads):
-    """Head stride of a bias in a's entry order, [nnz] or [H, nnz]; 0: one bias for all heads, or none."""
-    if bias is None:
-        return 0
-    if bias.dtype != torch.float32 or tuple(bias.shape) not in ((a.nnz,), (heads, a.nnz)) or (a.nnz > 1 and bias.stride(-1) != 1):
-        raise ValueError(f"bias must be a float32 tensor of shape ({a.nnz},) or ({heads}, {a.nnz}) with unit stride along the entries, "
-                         f"not {bias.dtype} {tuple(bias.shape)}")
-    if bias.dim() != 2 or heads == 1:
-        return 0
-    if bias.stride(0) < 0:
-        raise ValueError("bias must not have a negative head stride")
-    return bias.stride(0)
-
-
 def attention_csr(a, q, k, v, scale=None, bias=None, return_lse=False, out=None, lse=None, stream=None):
     """Fused attention on a CSR pattern (mispmm_attn_csr_f32, libmispmm_attn_csr.so): for every head, out = softmax over each
     row's stored entries of (scale * <q_r, k_c> + bias), times v -- one launch for all heads, neither the scores nor the
@@ -727,50 +683,9 @@ def attention_csr(a, q, k, v, scale=None, bias=None, return_lse=False, out=None,
     the heads, or [H, nnz], in A's entry order, added to the scaled scores, -Inf = masked.  Returns out, [M, Dv] or
     [H, M, Dv]; with return_lse (out, lse), lse the [M] or [H, M] log-sum-exp of each row.  out= and lse= take the results
     where given: out of the result's shape with unit column stride, lse contiguous."""
-    from . import capi_attn_csr
+    from . import _attn_csr
     _require_gpu(a.row_ptrs, q, k, v, bias, out, lse)
-    if a.data.dtype != torch.float32:
-        raise ValueError("attention_csr takes a float32 DeviceCSR")
-    if q.dim() != k.dim() or q.dim() != v.dim():
-        raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
-    batched = q.dim() == 3
-    (q3, ldq, q_head), (k3, ldk, k_head), (v3, ldv, v_head) = _attn_csr_qkv(a, q, k, v)
-    heads, d, dv = q3.shape[0], q3.shape[2], v3.shape[2]
-    bias_head = _attn_csr_bias_head(a, bias, heads)
-    if scale is None:
-        scale = d ** -0.5
-    shape = (heads, a.num_rows, dv)
-    if out is None:
-        out3 = torch.empty(shape, dtype=torch.float32, device=q.device)
-    else:
-        if out.dtype != torch.float32 or out.dim() != q.dim():
-            raise ValueError(f"out must be a float32 tensor of shape {shape if batched else shape[1:]} with unit column stride")
-        out3 = out if batched else out.unsqueeze(0)
-        if tuple(out3.shape) != shape or (dv > 1 and out3.stride(2) != 1) or (shape[1] > 1 and out3.stride(1) < dv) \
-                or (heads > 1 and out3.stride(0) < 1):
-            raise ValueError(f"out must be a float32 tensor of shape {shape if batched else shape[1:]} with unit column stride")
-    lse_shape = (heads, a.num_rows) if batched else (a.num_rows,)
-    if lse is None and return_lse:
-        lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
-    if lse is not None and (lse.dtype != torch.float32 or tuple(lse.shape) != lse_shape or not lse.is_contiguous()):
-        raise ValueError(f"lse must be a contiguous float32 tensor of shape {lse_shape}")
-    ldo = out3.stride(1) if shape[1] > 1 else max(dv, out3.stride(1))
-    o_head = out3.stride(0) if heads > 1 else 0
-    capi_attn_csr.check(capi_attn_csr.lib().mispmm_attn_csr_f32(
-        _stream_ptr(stream), heads, a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs), _p(q3), q_head, ldq, _p(k3), k_head, ldk, d,
-        _p(v3), v_head, ldv, dv, float(scale), _p(bias), bias_head, _p(out3), o_head, ldo, _p(lse)))
-    result = out if out is not None else (out3 if batched else out3[0])
-    return (result, lse) if return_lse else result
-
-
-def _attn_csr_result(t, shape, batched, what):
-    """(t as [H, rows, width], row stride, head stride) of a float32 tensor the backward reads or writes."""
-    t3 = t if batched else t.unsqueeze(0)
-    if t.dtype != torch.float32 or t.dim() != (3 if batched else 2) or tuple(t3.shape) != shape or (shape[2] > 1 and t3.stride(2) != 1) \
-            or (shape[1] > 1 and t3.stride(1) < shape[2]) or any(s < 0 for s in t3.stride()):
-        raise ValueError(f"{what} must be a float32 tensor of shape {shape if batched else shape[1:]} with unit column stride and rows that "
-                         f"do not overlap, not {t.dtype} {tuple(t.shape)} with strides {tuple(t.stride())}")
-    return t3, (t3.stride(1) if shape[1] > 1 else max(shape[2], t3.stride(1))), (t3.stride(0) if shape[0] > 1 else 0)
+    return _attn_csr.forward("attention_csr", _attn_csr.F32, a, q, k, v, scale, bias, False, return_lse, out, lse, stream)
 
 
 def attention_csr_bwd(a, at, perm, q, k, v, out, lse, grad_out, scale=None, bias=None, need=(True, True, True), dq=None, dk=None, dv=None,
@@ -784,56 +699,10 @@ def attention_csr_bwd(a, at, perm, q, k, v, out, lse, grad_out, scale=None, bias
     their work is skipped.  dk and dv are [H, K, ...] also where k and v are one head expanded over all.  dq= / dk= / dv= take
     the gradients where given.  delta: a contiguous float32 workspace of lse's shape, allocated here unless given; needed
     for dq and dk."""
-    from . import capi_attn_csr_bwd
+    from . import _attn_csr
     _require_gpu(a.row_ptrs, at.row_ptrs, perm, q, k, v, out, lse, grad_out, bias, dq, dk, dv, delta)
-    if a.data.dtype != torch.float32:
-        raise ValueError("attention_csr_bwd takes a float32 DeviceCSR")
-    if (at.num_rows, at.num_cols, at.nnz) != (a.num_cols, a.num_rows, a.nnz):
-        raise ValueError(f"at must be the pattern of A^T: {a.num_cols} x {a.num_rows} with {a.nnz} entries")
-    if len({q.dim(), k.dim(), v.dim(), out.dim(), grad_out.dim()}) != 1:
-        raise ValueError("q, k, v, out and grad_out must all be 2-D or all [H, ...]")
-    batched = q.dim() == 3
-    (q3, ldq, q_head), (k3, ldk, k_head), (v3, ldv, v_head) = _attn_csr_qkv(a, q, k, v)
-    heads, d, dvw = q3.shape[0], q3.shape[2], v3.shape[2]
-    o3, ldo, o_head = _attn_csr_result(out, (heads, a.num_rows, dvw), batched, "out")
-    g3, ldg, g_head = _attn_csr_result(grad_out, (heads, a.num_rows, dvw), batched, "grad_out")
-    rows_shape = (heads, a.num_rows) if batched else (a.num_rows,)
-    if lse.dtype != torch.float32 or tuple(lse.shape) != rows_shape or not lse.is_contiguous():
-        raise ValueError(f"lse must be a contiguous float32 tensor of shape {rows_shape}")
-    bias_head = _attn_csr_bias_head(a, bias, heads)
-    if len(need) != 3:
-        raise ValueError("need holds three flags: (dq, dk, dv)")
-    if perm is not None:
-        if perm.dtype not in (torch.int32, torch.int64) or perm.numel() != a.nnz:
-            raise ValueError(f"perm must hold {a.nnz} int32 or int64 entry numbers")
-        if perm.dtype == torch.int64:
-            perm = perm.to(torch.int32)
-        perm = perm.contiguous()
-    elif bias is not None and (need[1] or need[2]):
-        raise ValueError("with a bias, dk and dv need perm")
-    if scale is None:
-        scale = d ** -0.5
-    grads = []
-    for wanted, given, rows, width, what in ((need[0], dq, a.num_rows, d, "dq"), (need[1], dk, a.num_cols, d, "dk"), (need[2], dv, a.num_cols, dvw, "dv")):
-        if not wanted:
-            grads.append((None, None, 0, 0))
-            continue
-        shape = (heads, rows, width)
-        if given is None:
-            given = torch.empty(shape if batched else shape[1:], dtype=torch.float32, device=q.device)
-        t3, ld, head = _attn_csr_result(given, shape, batched, what)
-        grads.append((given, t3, ld, head))
-    if need[0] or need[1]:
-        if delta is None:
-            delta = torch.empty(rows_shape, dtype=torch.float32, device=q.device)
-        elif delta.dtype != torch.float32 or tuple(delta.shape) != rows_shape or not delta.is_contiguous():
-            raise ValueError(f"delta must be a contiguous float32 tensor of shape {rows_shape}")
-    (rq, q_out, lddq, dq_head), (rk, k_out, lddk, dk_head), (rv, v_out, lddv, dv_head) = grads
-    capi_attn_csr_bwd.check(capi_attn_csr_bwd.lib().mispmm_attn_csr_bwd_f32(
-        _stream_ptr(stream), heads, a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs), _p(at.row_ptrs), _p(at.col_idxs), _p(perm),
-        _p(q3), q_head, ldq, _p(k3), k_head, ldk, d, _p(v3), v_head, ldv, dvw, float(scale), _p(bias), bias_head, _p(o3), o_head, ldo, _p(lse),
-        _p(g3), g_head, ldg, _p(delta), _p(q_out), dq_head, lddq, _p(k_out), dk_head, lddk, _p(v_out), dv_head, lddv))
-    return rq, rk, rv
+    return _attn_csr.backward("attention_csr_bwd", _attn_csr.F32, a, at, perm, q, k, v, out, lse, grad_out, scale, bias, need, False, dq, dk, dv,
+                              delta, stream)
 
 
 @dataclass
