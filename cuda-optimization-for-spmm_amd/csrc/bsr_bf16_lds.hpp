@@ -30,16 +30,13 @@
 // instructions of an iteration (three DMA issues, five LDS reads and their wait, a barrier) are what a SIMD spends
 // its time on, and a deeper ring only removes resident workgroups.  Kept opt-in (MISPMM_BSR_LDS=1) and under test.
 #pragma once
+#include "bsr_mfma_tiles.hpp"
 #include "spmm_common.hpp"
 
 namespace mispmm {
 
 namespace bsr_lds {
-using f32x4_t = float __attribute__((ext_vector_type(4)));
-using bf16x8_t = short __attribute__((ext_vector_type(8)));
 using s16x4_t = short __attribute__((ext_vector_type(4)));
-using u32x2_t = uint32_t __attribute__((ext_vector_type(2)));
-using u32x4_t = uint32_t __attribute__((ext_vector_type(4)));
 using lds_ptr_t = __attribute__((address_space(3))) void *;
 
 constexpr uint32_t kSlotA = 0, kSlotP0 = 1024, kSlotP1 = 1024 + 2048, kSlotBytes = 1024 + 2 * 2048;

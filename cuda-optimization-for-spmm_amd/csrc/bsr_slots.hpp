@@ -16,6 +16,7 @@
 // (fixed) order.  Replaces the thread-per-block-element atomicAdd kernel of /root/reference/src/spmm/bsr/spmm_bsr_k1.cu:9-41
 // for BASELINE config 4 (bf16 is a new capability: the reference has none).
 #pragma once
+#include "bsr_mfma_tiles.hpp"
 #include "spmm_common.hpp"
 
 namespace mispmm {
@@ -60,9 +61,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     unsigned long long bstamp[7];
 #endif
     MISPMM_BSR_STAMP(0);
-    using f32x4_t = float __attribute__((ext_vector_type(4)));
-    using bf16x8_t = short __attribute__((ext_vector_type(8)));
-    using u32x4_t = uint32_t __attribute__((ext_vector_type(4)));
     constexpr int TPL = 8;
     // [wave - 1][row of the block row][128 columns]: 24 KiB.  No padding needed: a ds_write_b128 is served in groups of
     // 8 consecutive lanes = 256 contiguous bytes here, and so is the read back.
@@ -97,17 +95,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         for (int e = 0; e < 8; ++e) ix.v[e] = (lo[e] & m0) | (lo[8 + e] & m1) | (hi[e] & m2) | (hi[8 + e] & m3);
         return lo[0];
     };
-    // one MFMA K step (32 occupied columns) into fresh accumulators: tile t <-> output column 8c + t
+    // one MFMA K step (32 occupied columns) into fresh accumulators: tile t <-> output column 8c + t (bsr_mfma_tiles.hpp)
     auto step_tile = [&](uint32_t s, const Idx &ix, f32x4_t (&t)[TPL], bool stamp) {
         uint32_t braw[8][TPL / 2];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const uint32_t col = ix.v[e];
             // padding (0xFFFFFFFF) and lanes past N: a dropped read (zeros); the coefficients there are zero as well
-            const uint32_t voff = col == 0xFFFFFFFFu ? kDropLoad : col * ldb2 + lane_off;
-            const auto r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) braw[e][w] = r[w];
+            load_brow<TPL>(rsrc, col == 0xFFFFFFFFu ? kDropLoad : col * ldb2 + lane_off, braw[e]);
         }
         const u32x4_t araw = *reinterpret_cast<const u32x4_t *>(tiles + static_cast<size_t>(s) * 512u + c * 32u + g * 8u);
         // all nine reads are on their way before the first v_perm: without this fence hipcc interleaves the operand
@@ -124,12 +119,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 #pragma unroll
         for (int w = 0; w < TPL / 2; ++w) {
             u32x4_t even, odd;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const uint32_t l2 = braw[2 * p][w], h2 = braw[2 * p + 1][w];
-                even[p] = __builtin_amdgcn_perm(h2, l2, 0x05040100u);  // {hi.h0, lo.h0}
-                odd[p] = __builtin_amdgcn_perm(h2, l2, 0x07060302u);   // {hi.h1, lo.h1}
-            }
+            regroup_pair<TPL>(braw, w, even, odd);
             t[2 * w] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, __builtin_bit_cast(bf16x8_t, even), zero, 0, 0, 0);
             t[2 * w + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, __builtin_bit_cast(bf16x8_t, odd), zero, 0, 0, 0);
         }
@@ -158,12 +148,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     auto store_row = [&](uint32_t row, const f32x4_t &s0, const f32x4_t &s1) {
         const size_t crow = static_cast<size_t>(row) * ldc + ncol;
         if constexpr (C_BF16) {
-            using bf2 = __bf16 __attribute__((ext_vector_type(2)));
             u32x4_t o;
-            o[0] = __builtin_bit_cast(uint32_t, bf2{static_cast<__bf16>(s0[0]), static_cast<__bf16>(s0[1])});
-            o[1] = __builtin_bit_cast(uint32_t, bf2{static_cast<__bf16>(s0[2]), static_cast<__bf16>(s0[3])});
-            o[2] = __builtin_bit_cast(uint32_t, bf2{static_cast<__bf16>(s1[0]), static_cast<__bf16>(s1[1])});
-            o[3] = __builtin_bit_cast(uint32_t, bf2{static_cast<__bf16>(s1[2]), static_cast<__bf16>(s1[3])});
+            o[0] = pack_bf2(s0[0], s0[1]);
+            o[1] = pack_bf2(s0[2], s0[3]);
+            o[2] = pack_bf2(s1[0], s1[1]);
+            o[3] = pack_bf2(s1[2], s1[3]);
             if constexpr (ST >= 0) {
                 __builtin_amdgcn_raw_buffer_store_b128(o, make_rsrc(Cv, c_bytes), static_cast<uint32_t>(crow * 2u), 0, ST);
             } else {

@@ -16,6 +16,9 @@
 //   bsr_mfma_bf16  16x16 bf16 blocks on v_mfma_f32_16x16x32_bf16, two blocks per instruction
 //             (K = 32), fp32 accumulate, B transposed into operand order in registers (v_perm);
 //             the 4 waves of a workgroup split a block row's pairs and reduce through LDS.
+//             Its tile pieces -- vector types, fragment record, B-row read, operand regroup, C-row
+//             store, and the lane layout they share -- stand once in bsr_mfma_tiles.hpp, for it,
+//             bsr_mfma_bf16_b32, bsrc_mfma_bf16 and bsrc_slots_mfma_bf16 (bsr_slots.hpp).
 // Output columns of a 64-wide super-tile are interleaved over the 4 accumulator tiles
 // (tile t, lane column c <-> column 4c + t), so B rows are read and C rows written as whole
 // 16-byte (fp32) / 8-byte (bf16) vectors.
@@ -24,15 +27,11 @@
 #include <cstdlib>
 
 #include "bsr_bf16_lds.hpp"
+#include "bsr_mfma_tiles.hpp"
 #include "bsr_slots.hpp"
 #include "spmm_common.hpp"
 
 namespace mispmm {
-
-using f32x4_t = float __attribute__((ext_vector_type(4)));
-using bf16x8_t = short __attribute__((ext_vector_type(8)));
-using u32x2_t = uint32_t __attribute__((ext_vector_type(2)));
-using u32x4_t = uint32_t __attribute__((ext_vector_type(4)));
 
 // -------------------------------------------------------------------------------------- bsr_valu
 template <int G, int VEC, class Acc, bool WIDE>
@@ -302,19 +301,11 @@ __global__ __launch_bounds__(256) void bsr_mfma_f32(uint32_t Mb, uint32_t nST, c
 // One WORKGROUP per (block row, super-tile of 16 * TPL output columns); its 4 waves split the block
 // row's block pairs round-robin (pair p -> wave p % 4), each keeps a partial 16 x (16 * TPL) fp32
 // tile, and the partials are summed through LDS in fixed wave order (deterministic) before the
-// store.  MFMA 16x16x32 bf16: lane (c, g) holds A[i = c][k = 8g .. 8g+7] and B[k = 8g .. 8g+7][j = c].
+// store.  Lane layout, column interleave, B-row read, regroup and C-row store: bsr_mfma_tiles.hpp.
 // k slots 0..15 are the 16 columns of the pair's first block, slots 16..31 those of its second
-// block (zero when an odd block is left over).  A lane reads, for each of its 8 k rows, the TPL
-// consecutive bf16 of columns TPL*c .. TPL*c + TPL-1 (one per accumulator tile: 16 bytes at
-// TPL = 8, so one wave-instruction covers 128 columns of 4 B rows) and regroups them per tile with
-// v_perm_b32: the transpose B needs, done in registers.  Optional two-deep software pipeline (PIPE).  TPL = 8 (N >= 128) halves the B-read instruction count of TPL = 4: the kernel is bound by
+// block (zero when an odd block is left over).  At TPL = 8 one wave-instruction covers 128 columns
+// of 4 B rows.  Optional two-deep software pipeline (PIPE).  TPL = 8 (N >= 128) halves the B-read instruction count of TPL = 4: the kernel is bound by
 // the texture-address path (33 100 blocks each pull a 16 x N panel), not by MFMA or HBM.
-template <int TPL>
-struct Bf16Frag {
-    u32x4_t araw;
-    uint32_t braw[8][TPL / 2];
-};
-
 template <int TPL, bool C_BF16, bool PIPE = true, int WAVES = 4>
 __global__ __launch_bounds__(64 * WAVES, PIPE ? 1 : (WAVES == 4 ? 5 : 4)) void bsr_mfma_bf16(uint32_t Mb, uint32_t nST, const uint32_t *__restrict__ blockRowPtrs,
                                                      const uint32_t *__restrict__ blockColIdxs,
@@ -343,40 +334,22 @@ __global__ __launch_bounds__(64 * WAVES, PIPE ? 1 : (WAVES == 4 ? 5 : 4)) void b
     if (wave < npairs) {
         const uint32_t last = be - 1;
         auto block_of = [&](uint32_t pair) { return bs + 2 * pair + second; };
-        auto load_frag = [&](uint32_t pair, uint32_t bcol, Bf16Frag<TPL> &f) {
+        auto load_frag = [&](uint32_t pair, uint32_t bcol, Frag<TPL> &f) {
             const uint32_t b = block_of(pair);
             const bool have = b <= last;  // false for the missing half of an odd pair and past the row
-            f.araw = *reinterpret_cast<const u32x4_t *>(blocks + static_cast<size_t>(min(b, last)) * 256u + c * 16u + khalf);
-            if (!have) f.araw = u32x4_t{0u, 0u, 0u, 0u};
-            // the block column differs between the two halves of the wave, so the whole row offset
-            // is per-lane (voffset); soffset stays 0 (a non-uniform soffset costs a waterfall loop)
+            f.araw[0] = *reinterpret_cast<const u32x4_t *>(blocks + static_cast<size_t>(min(b, last)) * 256u + c * 16u + khalf);
+            if (!have) f.araw[0] = u32x4_t{0u, 0u, 0u, 0u};
+            // the block column differs between the two halves of the wave, so the whole row offset is per-lane
             const uint32_t voff = have ? lane_off + (bcol * 16u + khalf) * ldb2 : kDropLoad;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                if constexpr (TPL == 8) {
-                    const auto r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + e * ldb2, 0, 0);
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) f.braw[e][w] = r[w];
-                } else {
-                    const auto r = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff + e * ldb2, 0, 0);
-                    f.braw[e][0] = r[0];
-                    f.braw[e][1] = r[1];
-                }
-            }
+            for (int e = 0; e < 8; ++e) load_brow<TPL>(rsrc, voff + e * ldb2, f.braw[e]);
         };
-        auto multiply = [&](const Bf16Frag<TPL> &f) {
-            const bf16x8_t afrag = __builtin_bit_cast(bf16x8_t, f.araw);
+        auto multiply = [&](const Frag<TPL> &f) {
+            const bf16x8_t afrag = __builtin_bit_cast(bf16x8_t, f.araw[0]);
 #pragma unroll
             for (int w = 0; w < TPL / 2; ++w) {
-                // tiles 2w and 2w+1 take the low and high bf16 of dword w of every k row; once both are packed the
-                // eight raw dwords are dead, so the regrouped operands never coexist with more than one dword column
                 u32x4_t even, odd;
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const uint32_t lo = f.braw[2 * p][w], hi = f.braw[2 * p + 1][w];
-                    even[p] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);  // {hi.h0, lo.h0}
-                    odd[p] = __builtin_amdgcn_perm(hi, lo, 0x07060302u);   // {hi.h1, lo.h1}
-                }
+                regroup_pair<TPL>(f.braw, w, even, odd);
                 acc[2 * w] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, __builtin_bit_cast(bf16x8_t, even), acc[2 * w], 0, 0, 0);
                 acc[2 * w + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, __builtin_bit_cast(bf16x8_t, odd), acc[2 * w + 1], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
@@ -384,11 +357,11 @@ __global__ __launch_bounds__(64 * WAVES, PIPE ? 1 : (WAVES == 4 ? 5 : 4)) void b
         };
         if constexpr (PIPE) {
             uint32_t col_next = blockColIdxs[min(block_of(wave + WAVES), last)];
-            Bf16Frag<TPL> cur;
+            Frag<TPL> cur;
             load_frag(wave, blockColIdxs[min(block_of(wave), last)], cur);
             for (uint32_t pair = wave; pair < npairs; pair += WAVES) {
                 const uint32_t col_next2 = blockColIdxs[min(block_of(pair + 2 * WAVES), last)];
-                Bf16Frag<TPL> nxt;
+                Frag<TPL> nxt;
                 load_frag(pair + WAVES, col_next, nxt);
                 multiply(cur);
                 cur = nxt;
@@ -402,7 +375,7 @@ __global__ __launch_bounds__(64 * WAVES, PIPE ? 1 : (WAVES == 4 ? 5 : 4)) void b
             uint32_t col_cur = blockColIdxs[min(block_of(wave), last)];
             for (uint32_t pair = wave; pair < npairs; pair += WAVES) {
                 const uint32_t col_next = blockColIdxs[min(block_of(pair + WAVES), last)];
-                Bf16Frag<TPL> cur;
+                Frag<TPL> cur;
                 load_frag(pair, col_cur, cur);
                 multiply(cur);
                 col_cur = col_next;
@@ -423,25 +396,7 @@ __global__ __launch_bounds__(64 * WAVES, PIPE ? 1 : (WAVES == 4 ? 5 : 4)) void b
     }
     if (ncol < N) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const size_t crow = static_cast<size_t>(R * 16 + g * 4 + r) * ldc + ncol;
-            if constexpr (C_BF16) {
-                using bf2 = __bf16 __attribute__((ext_vector_type(2)));
-                uint32_t o[TPL / 2];
-#pragma unroll
-                for (int w = 0; w < TPL / 2; ++w)
-                    o[w] = __builtin_bit_cast(uint32_t, bf2{static_cast<__bf16>(acc[2 * w][r]), static_cast<__bf16>(acc[2 * w + 1][r])});
-                uint16_t *dst = static_cast<uint16_t *>(Cv) + crow;
-                if constexpr (TPL == 8) *reinterpret_cast<u32x4_t *>(dst) = u32x4_t{o[0], o[1], o[2], o[3]};
-                else *reinterpret_cast<u32x2_t *>(dst) = u32x2_t{o[0], o[1]};
-            } else {
-                float *dst = static_cast<float *>(Cv) + crow;
-#pragma unroll
-                for (int w = 0; w < TPL / 4; ++w)
-                    *reinterpret_cast<f32x4_t *>(dst + 4 * w) =
-                        f32x4_t{acc[4 * w][r], acc[4 * w + 1][r], acc[4 * w + 2][r], acc[4 * w + 3][r]};
-            }
-        }
+        for (int r = 0; r < 4; ++r) store_crow<TPL, C_BF16>(Cv, R * 16 + g * 4 + r, ldc, ncol, acc, r);
     }
 }
 
@@ -454,8 +409,7 @@ __global__ __launch_bounds__(64 * WAVES, PIPE ? 1 : (WAVES == 4 ? 5 : 4)) void b
 // block row instead of 13.2 block pairs), each B row fetched by its own index.  One WAVE owns a (block row, 128
 // output columns) item: no cross-wave reduction, no LDS, no barrier; a two-deep register pipeline keeps the next
 // step's 8 B-row reads (16 bytes per lane each) and its A tile in flight while this step's eight tiles are multiplied.
-// Lane (c, g): A operand row c, k 8g .. 8g+7 of the step; B operand rows cols[8g .. 8g+7], its TPL = 8 interleaved
-// output columns 8c .. 8c+7 (tile t <-> column 8c + t), regrouped per tile with v_perm_b32 as in bsr_mfma_bf16.
+// Lane (c, g) as in bsr_mfma_tiles.hpp at TPL = 8: A operand row c, k 8g .. 8g+7 of the step; B operand rows cols[8g .. 8g+7].
 // Terms of an output element are summed in ascending k = storage order of the occupied columns; deterministic.
 template <bool C_BF16>
 __global__ __launch_bounds__(256) void bsrc_mfma_bf16(uint32_t Mb, uint32_t nST, const uint32_t *__restrict__ stepPtrs,
@@ -479,38 +433,26 @@ __global__ __launch_bounds__(256) void bsrc_mfma_bf16(uint32_t Mb, uint32_t nST,
     for (int t = 0; t < TPL; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const uint32_t s0 = stepPtrs[R], s1 = stepPtrs[R + 1];
 
-    struct Step {
-        u32x4_t araw;
-        uint32_t braw[8][TPL / 2];
-    };
     auto load_idx = [&](uint32_t s, u32x4_t &lo, u32x4_t &hi) {  // this lane's 8 B-row indices of step s
         const u32x4_t *p = reinterpret_cast<const u32x4_t *>(cols + static_cast<size_t>(s) * 32u + g * 8u);
         lo = p[0];
         hi = p[1];
     };
-    auto load_step = [&](uint32_t s, const u32x4_t &lo, const u32x4_t &hi, Step &f) {
-        f.araw = *reinterpret_cast<const u32x4_t *>(tiles + static_cast<size_t>(s) * 512u + c * 32u + g * 8u);
+    auto load_step = [&](uint32_t s, const u32x4_t &lo, const u32x4_t &hi, Frag<TPL> &f) {
+        f.araw[0] = *reinterpret_cast<const u32x4_t *>(tiles + static_cast<size_t>(s) * 512u + c * 32u + g * 8u);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const uint32_t col = e < 4 ? lo[e] : hi[e - 4];
             // padding (0xFFFFFFFF) and lanes past N: a dropped read (zeros); the coefficients there are zero as well
-            const uint32_t voff = col == 0xFFFFFFFFu ? kDropLoad : col * ldb2 + lane_off;
-            const auto r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) f.braw[e][w] = r[w];
+            load_brow<TPL>(rsrc, col == 0xFFFFFFFFu ? kDropLoad : col * ldb2 + lane_off, f.braw[e]);
         }
     };
-    auto multiply = [&](const Step &f) {
-        const bf16x8_t afrag = __builtin_bit_cast(bf16x8_t, f.araw);
+    auto multiply = [&](const Frag<TPL> &f) {
+        const bf16x8_t afrag = __builtin_bit_cast(bf16x8_t, f.araw[0]);
 #pragma unroll
         for (int w = 0; w < TPL / 2; ++w) {
             u32x4_t even, odd;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const uint32_t lo = f.braw[2 * p][w], hi = f.braw[2 * p + 1][w];
-                even[p] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);  // {hi.h0, lo.h0}
-                odd[p] = __builtin_amdgcn_perm(hi, lo, 0x07060302u);   // {hi.h1, lo.h1}
-            }
+            regroup_pair<TPL>(f.braw, w, even, odd);
             acc[2 * w] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, __builtin_bit_cast(bf16x8_t, even), acc[2 * w], 0, 0, 0);
             acc[2 * w + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, __builtin_bit_cast(bf16x8_t, odd), acc[2 * w + 1], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
@@ -521,10 +463,10 @@ __global__ __launch_bounds__(256) void bsrc_mfma_bf16(uint32_t Mb, uint32_t nST,
         u32x4_t ilo, ihi, nlo, nhi;
         load_idx(s0, ilo, ihi);
         load_idx(min(s0 + 1, last), nlo, nhi);
-        Step cur;
+        Frag<TPL> cur;
         load_step(s0, ilo, ihi, cur);
         for (uint32_t s = s0; s < s1; ++s) {
-            Step nxt;
+            Frag<TPL> nxt;
             const bool more = s + 1 < s1;  // wave-uniform
             if (more) load_step(s + 1, nlo, nhi, nxt);
             load_idx(min(s + 2, last), nlo, nhi);
@@ -534,35 +476,16 @@ __global__ __launch_bounds__(256) void bsrc_mfma_bf16(uint32_t Mb, uint32_t nST,
     }
     if (ncol < N) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const size_t crow = static_cast<size_t>(R * 16 + g * 4 + r) * ldc + ncol;
-            if constexpr (C_BF16) {
-                using bf2 = __bf16 __attribute__((ext_vector_type(2)));
-                uint32_t o[TPL / 2];
-#pragma unroll
-                for (int w = 0; w < TPL / 2; ++w)
-                    o[w] = __builtin_bit_cast(uint32_t, bf2{static_cast<__bf16>(acc[2 * w][r]), static_cast<__bf16>(acc[2 * w + 1][r])});
-                *reinterpret_cast<u32x4_t *>(static_cast<uint16_t *>(Cv) + crow) = u32x4_t{o[0], o[1], o[2], o[3]};
-            } else {
-                float *dst = static_cast<float *>(Cv) + crow;
-#pragma unroll
-                for (int w = 0; w < TPL / 4; ++w)
-                    *reinterpret_cast<f32x4_t *>(dst + 4 * w) = f32x4_t{acc[4 * w][r], acc[4 * w + 1][r], acc[4 * w + 2][r], acc[4 * w + 3][r]};
-            }
-        }
+        for (int r = 0; r < 4; ++r) store_crow<TPL, C_BF16>(Cv, R * 16 + g * 4 + r, ldc, ncol, acc, r);
     }
 }
 
 // ----------------------------------------------------------------------------- bsr_mfma_bf16_b32
 // 32 x 32 blocks: a block's 32 columns are exactly the K = 32 of one v_mfma_f32_16x16x32_bf16, so no
 // pairing; its 32 rows are two 16-row halves that share the B fragment (one B fetch, two MFMAs per
-// tile).  Work split, column interleave, pipeline and LDS reduction as in the 16 x 16 kernel.
-template <int TPL>
-struct Bf16Frag32 {
-    u32x4_t araw[2];
-    uint32_t braw[8][TPL / 2];
-};
-
+// tile, acc[0][t] before acc[1][t] for ascending t).  One WORKGROUP per (block row, super-tile), its 4 waves take the
+// blocks round-robin behind a two-deep register pipeline and reduce through LDS in fixed wave order; the lane layout
+// and the tile pieces are bsr_mfma_tiles.hpp's, with two A operands per fragment.
 template <int TPL, bool C_BF16>
 __global__ __launch_bounds__(256) void bsr_mfma_bf16_b32(uint32_t Mb, uint32_t nST, const uint32_t *__restrict__ blockRowPtrs,
                                                          const uint32_t *__restrict__ blockColIdxs,
@@ -590,45 +513,33 @@ __global__ __launch_bounds__(256) void bsr_mfma_bf16_b32(uint32_t Mb, uint32_t n
     const uint32_t bs = blockRowPtrs[R], be = blockRowPtrs[R + 1];
     if (bs + wave < be) {
         const uint32_t last = be - 1;
-        auto load_frag = [&](uint32_t b, uint32_t bcol, Bf16Frag32<TPL> &f) {
+        auto load_frag = [&](uint32_t b, uint32_t bcol, Frag<TPL, 2> &f) {
             const bool have = b <= last;
             const uint16_t *ablk = blocks + static_cast<size_t>(min(b, last)) * 1024u + c * 32u + g * 8u;
             f.araw[0] = *reinterpret_cast<const u32x4_t *>(ablk);
             f.araw[1] = *reinterpret_cast<const u32x4_t *>(ablk + 16 * 32);
             const uint32_t voff = have ? lane_off + (bcol * 32u + g * 8u) * ldb2 : kDropLoad;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                if constexpr (TPL == 8) {
-                    const auto r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + e * ldb2, 0, 0);
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) f.braw[e][w] = r[w];
-                } else {
-                    const auto r = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff + e * ldb2, 0, 0);
-                    f.braw[e][0] = r[0];
-                    f.braw[e][1] = r[1];
-                }
-            }
+            for (int e = 0; e < 8; ++e) load_brow<TPL>(rsrc, voff + e * ldb2, f.braw[e]);
         };
         uint32_t col_next = blockColIdxs[min(bs + wave + 4, last)];
-        Bf16Frag32<TPL> cur;
+        Frag<TPL, 2> cur;
         load_frag(bs + wave, blockColIdxs[bs + wave], cur);
         for (uint32_t b = bs + wave; b < be; b += 4) {
             const uint32_t col_next2 = blockColIdxs[min(b + 8, last)];
-            Bf16Frag32<TPL> nxt;
+            Frag<TPL, 2> nxt;
             load_frag(b + 4, col_next, nxt);  // dropped B reads past the row; the A it re-reads is never used
             const bf16x8_t a0 = __builtin_bit_cast(bf16x8_t, cur.araw[0]);
             const bf16x8_t a1 = __builtin_bit_cast(bf16x8_t, cur.araw[1]);
 #pragma unroll
-            for (int t = 0; t < TPL; ++t) {
-                u32x4_t packed;
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const uint32_t lo = cur.braw[2 * p][t >> 1], hi = cur.braw[2 * p + 1][t >> 1];
-                    packed[p] = (t & 1) ? __builtin_amdgcn_perm(hi, lo, 0x07060302u) : __builtin_amdgcn_perm(hi, lo, 0x05040100u);
-                }
-                const bf16x8_t bfrag = __builtin_bit_cast(bf16x8_t, packed);
-                acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bfrag, acc[0][t], 0, 0, 0);
-                acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bfrag, acc[1][t], 0, 0, 0);
+            for (int w = 0; w < TPL / 2; ++w) {
+                u32x4_t even, odd;
+                regroup_pair<TPL>(cur.braw, w, even, odd);
+                const bf16x8_t b0 = __builtin_bit_cast(bf16x8_t, even), b1 = __builtin_bit_cast(bf16x8_t, odd);
+                acc[0][2 * w] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[0][2 * w], 0, 0, 0);
+                acc[1][2 * w] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0, acc[1][2 * w], 0, 0, 0);
+                acc[0][2 * w + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1, acc[0][2 * w + 1], 0, 0, 0);
+                acc[1][2 * w + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc[1][2 * w + 1], 0, 0, 0);
             }
             cur = nxt;
             col_next = col_next2;
@@ -652,26 +563,8 @@ __global__ __launch_bounds__(256) void bsr_mfma_bf16_b32(uint32_t Mb, uint32_t n
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const size_t crow = static_cast<size_t>(R * 32 + h * 16 + g * 4 + r) * ldc + ncol;
-                if constexpr (C_BF16) {
-                    using bf2 = __bf16 __attribute__((ext_vector_type(2)));
-                    uint32_t o[TPL / 2];
-#pragma unroll
-                    for (int w = 0; w < TPL / 2; ++w)
-                        o[w] = __builtin_bit_cast(uint32_t, bf2{static_cast<__bf16>(acc[h][2 * w][r]),
-                                                                static_cast<__bf16>(acc[h][2 * w + 1][r])});
-                    uint16_t *dst = static_cast<uint16_t *>(Cv) + crow;
-                    if constexpr (TPL == 8) *reinterpret_cast<u32x4_t *>(dst) = u32x4_t{o[0], o[1], o[2], o[3]};
-                    else *reinterpret_cast<u32x2_t *>(dst) = u32x2_t{o[0], o[1]};
-                } else {
-                    float *dst = static_cast<float *>(Cv) + crow;
-#pragma unroll
-                    for (int w = 0; w < TPL / 4; ++w)
-                        *reinterpret_cast<f32x4_t *>(dst + 4 * w) =
-                            f32x4_t{acc[h][4 * w][r], acc[h][4 * w + 1][r], acc[h][4 * w + 2][r], acc[h][4 * w + 3][r]};
-                }
-            }
+            for (int r = 0; r < 4; ++r)
+                store_crow<TPL, C_BF16>(Cv, R * 32 + h * 16 + g * 4 + r, ldc, ncol, acc[h], r);
         }
     }
 }
@@ -738,6 +631,24 @@ static bool mfma_shape_ok(uint32_t K, uint32_t N, uint32_t ldb, uint32_t ldc, co
            fits_buffer(K, ldb, static_cast<uint32_t>(elem));
 }
 
+// what the three bf16 entry points share: the leading-dimension refusal under the entry point's name `fn` (0 = passed) ...
+static int refuse_ld(const char *fn, uint32_t N, uint32_t ldb, uint32_t ldc) {
+    if (ldb < N || ldc < N) return fail(MISPMM_ERR_INVALID_ARG, "%s: leading dimension smaller than N", fn);
+    return MISPMM_OK;
+}
+// ... and the extent of B for its buffer descriptor (below 2 GiB once the shape checks have passed)
+static uint32_t bf16_bytes(uint32_t K, uint32_t ldb) { return static_cast<uint32_t>(static_cast<uint64_t>(K) * ldb * 2u); }
+
+// the shapes the two column-compacted entry points take: 128-column super-tiles read and written as 16-byte vectors
+static int refuse_bsrc_shape(const char *fn, uint32_t K, uint32_t N, uint32_t ldb, uint32_t ldc, const void *B, const void *C,
+                             const void *tiles, const void *cols) {
+    if (int s = refuse_ld(fn, N, ldb, ldc)) return s;
+    if (N % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0 || !aligned16(B) || !aligned16(C) || !aligned16(tiles) || !aligned16(cols) ||
+        !fits_buffer(K, ldb, 2))
+        return fail(MISPMM_ERR_UNSUPPORTED, "%s: N / ldb / ldc must be multiples of 8, operands 16-byte aligned, B below 2 GiB", fn);
+    return MISPMM_OK;
+}
+
 }  // namespace mispmm
 
 using namespace mispmm;
@@ -784,7 +695,7 @@ extern "C" int mispmm_bsr_bf16(mispmm_stream_t stream, uint32_t numBlockRows, ui
     if (numBlockRows == 0 || N == 0) return MISPMM_OK;
     if (!blockRowPtrs || !B || !C) return fail(MISPMM_ERR_INVALID_ARG, "bsr_bf16: null pointer");
     if (numBlocks != 0 && (!blockColIdxs || !blocks)) return fail(MISPMM_ERR_INVALID_ARG, "bsr_bf16: null block arrays");
-    if (ldb < N || ldc < N) return fail(MISPMM_ERR_INVALID_ARG, "bsr_bf16: leading dimension smaller than N");
+    if (int s = refuse_ld("bsr_bf16", N, ldb, ldc)) return s;
     if (!mfma_shape_ok(K, N, ldb, ldc, B, C, blocks, 2) || (!c_bf16 && !aligned16(C)))
         return fail(MISPMM_ERR_UNSUPPORTED, "bsr_bf16: N/ldb/ldc must be multiples of 4 and operands vector-aligned");
     // 8 tiles per lane (128-column super-tiles, 16-byte B reads) once N fills them and 16-byte vectors
@@ -793,7 +704,7 @@ extern "C" int mispmm_bsr_bf16(mispmm_stream_t stream, uint32_t numBlockRows, ui
     const uint32_t nST = ceil_div(N, wide ? 128u : 64u);
     const XcdGrid xg = xcd_grid(numBlockRows * nST);  // one workgroup per (block row, super-tile)
     dim3 grid(xg.grid);
-    const uint32_t b_bytes = static_cast<uint32_t>(static_cast<uint64_t>(K) * ldb * 2u);
+    const uint32_t b_bytes = bf16_bytes(K, ldb);
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, as_stream(stream), numBlockRows, nST, blockRowPtrs, blockColIdxs, blocks, B, b_bytes, N, ldb,
                            C, ldc, xg.chunk);
@@ -850,13 +761,10 @@ extern "C" int mispmm_bsrc_bf16(mispmm_stream_t stream, uint32_t numBlockRows, u
     if (numBlockRows == 0 || N == 0) return MISPMM_OK;
     if (!stepPtrs || !B || !C) return fail(MISPMM_ERR_INVALID_ARG, "bsrc_bf16: null pointer");
     if (nSteps != 0 && (!cols || !tiles)) return fail(MISPMM_ERR_INVALID_ARG, "bsrc_bf16: null step arrays");
-    if (ldb < N || ldc < N) return fail(MISPMM_ERR_INVALID_ARG, "bsrc_bf16: leading dimension smaller than N");
-    if (N % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0 || !aligned16(B) || !aligned16(C) || !aligned16(tiles) || !aligned16(cols) ||
-        !fits_buffer(K, ldb, 2))
-        return fail(MISPMM_ERR_UNSUPPORTED, "bsrc_bf16: N / ldb / ldc must be multiples of 8, operands 16-byte aligned, B below 2 GiB");
+    if (int s = refuse_bsrc_shape("bsrc_bf16", K, N, ldb, ldc, B, C, tiles, cols)) return s;
     const uint32_t nST = ceil_div(N, 128u);
     const XcdGrid xg = xcd_grid(ceil_div(numBlockRows * nST, 4u));
-    const uint32_t b_bytes = static_cast<uint32_t>(static_cast<uint64_t>(K) * ldb * 2u);
+    const uint32_t b_bytes = bf16_bytes(K, ldb);
     note_kernel("bsrc_mfma_bf16<%s>", c_bf16 ? "c16" : "c32");
     with_flag(c_bf16 != 0, [&](auto cb) {
         hipLaunchKernelGGL((bsrc_mfma_bf16<decltype(cb)::value>), dim3(xg.grid), dim3(256), 0, as_stream(stream), numBlockRows, nST, stepPtrs, cols,
@@ -877,13 +785,10 @@ extern "C" int mispmm_bsrc_slots_bf16(mispmm_stream_t stream, uint32_t numBlockR
         return fail(MISPMM_ERR_INVALID_ARG, "bsrc_slots_bf16: nSteps %u is less than %u slots per block row", nSteps, kBsrSlots);
     if (static_cast<uint64_t>(numBlockRows) * ceil_div(N, 128u) > 0x7FFFFFFFull)   // one workgroup per (block row, 128 columns)
         return fail(MISPMM_ERR_UNSUPPORTED, "bsrc_slots_bf16: %u block rows x %u columns exceed the grid of this kernel", numBlockRows, N);
-    if (ldb < N || ldc < N) return fail(MISPMM_ERR_INVALID_ARG, "bsrc_slots_bf16: leading dimension smaller than N");
-    if (N % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0 || !aligned16(B) || !aligned16(C) || !aligned16(tiles) || !aligned16(cols) ||
-        !fits_buffer(K, ldb, 2))
-        return fail(MISPMM_ERR_UNSUPPORTED, "bsrc_slots_bf16: N / ldb / ldc must be multiples of 8, operands 16-byte aligned, B below 2 GiB");
+    if (int s = refuse_bsrc_shape("bsrc_slots_bf16", K, N, ldb, ldc, B, C, tiles, cols)) return s;
     const uint32_t nST = ceil_div(N, 128u);
     const XcdGrid xg = xcd_grid(numBlockRows * nST);  // one workgroup per (block row, 128 columns)
-    const uint32_t b_bytes = static_cast<uint32_t>(static_cast<uint64_t>(K) * ldb * 2u);
+    const uint32_t b_bytes = bf16_bytes(K, ldb);
     const uint64_t c_bytes = static_cast<uint64_t>(numBlockRows) * 16u * ldc * (c_bf16 ? 2u : 4u);
     // C store policy: MISPMM_BSR_STORE = -1 plain global stores, 2 non-temporal, 16 write-through (sc1), 18 both
     // (measurement aid; buffer stores need C below 2 GiB, else plain)
