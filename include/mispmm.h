@@ -421,6 +421,25 @@ int mispmm_bsrc_slots_bf16(mispmm_stream_t stream, uint32_t numBlockRows, uint32
                            const uint32_t *cols, const uint16_t *tiles, const uint16_t *B, uint32_t N, uint32_t ldb, void *C,
                            uint32_t ldc, int c_bf16);
 
+/* NUMERICS of mispmm_bsr_bf16, mispmm_bsrc_bf16 and mispmm_bsrc_slots_bf16, with `exact` the real-number sum of an element's
+ * stored terms (bf16 operands) and S = sum |a||b| over them:
+ *   fp32 C   |C - exact| <= g_n S, g_n = n u / (1 - n u), u = 2^-23 per addition;
+ *   bf16 C   C lies in the interval [exact - g_n S, exact + g_n S] rounded to bf16 (nearest even) at both ends: the fp32 sum
+ *            rounded once, a NaN stays a NaN.
+ *   n = (the element's products that are not zero) + (MFMA steps its wave runs for that block row) + (partial tiles added
+ *   across waves).  The product of two bf16 values is exact in fp32, and adding an exact zero rounds nothing.  Steps of the
+ *   busiest wave: mispmm_bsr_bf16 deals block pairs (16 x 16) or blocks (32 x 32) round-robin over 4 waves, ceil(ceil(blocks
+ *   / 2) / 4) or ceil(blocks / 4); mispmm_bsrc_bf16 runs all steps of a block row on one wave and adds no partial tiles;
+ *   mispmm_bsrc_slots_bf16 runs one slot and at most ceil(extra / 3) extra steps.  The others add 3 partial tiles.
+ *   Where every partial sum in every order is an fp32 number (operands of 8 bits in [0.5, 2) with S < 2^8, small integers)
+ *   the fp32 C is exact and the bf16 C its nearest-even rounding.
+ *   NaN / Inf: C[i][j] is NaN or +-Inf exactly where the sum of its terms is.  mispmm_bsr_bf16 (all of its kernels) multiplies
+ *   every stored element of a block, so an explicit zero of A forms 0 * b and 0 * Inf is NaN; the two compacted products
+ *   multiply the 16 rows of every occupied column of a block row -- a column in which some row holds a value that is not zero
+ *   as bf16 -- an explicit zero in such a column included, and never read a B row for any other column.  No product reads a
+ *   B row for a padding column, for the missing half of an odd block pair or past a block row's end.
+ *   An empty block row is written as +0; with ldc > N the elements between N and ldc are not written. */
+
 /* -------------------------------------------------------------- COO x dense */
 /* Row-major-sorted COO (the order convert_mtx.py:172-190 writes).  PRECONDITION: rowIdxs is
  * non-decreasing -- an unsorted array makes the row boundaries meaningless and the kernel read out of
