@@ -45,6 +45,7 @@ spmm_bf16(sddmm="bf16") uses), a head-summed bias gradient from the kernel (a bi
 summed by torch), the column-compacted block layouts (their tiles are built on the host from the values), a device kernel for
 the blocks[perm] transpose."""
 import dataclasses
+import functools
 from dataclasses import dataclass
 
 import numpy as np
@@ -550,14 +551,18 @@ class _FusedBlockSparseAttention(torch.autograd.Function):
     backward recomputes S and P head by head with the kernels of the three-launch forward -- to the bits that forward would
     have saved -- and runs its gradient chain."""
     @staticmethod
-    def forward(ctx, q, k, v, a, scale, mask, out_bf16, fused_backward=False):
+    def forward(ctx, q, k, v, a, scale, mask, out_bf16, fused_backward=False, splits=None):
         q, k, v = q.detach(), k.detach(), v.detach()
         ctx.a, ctx.scale, ctx.mask, ctx.fused_backward = a, scale, mask, fused_backward
+        attend = ops.attention_bsr_bf16
+        if splits is not None:                 # every block row dealt to several waves: two launches (attn_bsr_split.py)
+            from . import attn_bsr_split
+            attend = functools.partial(attn_bsr_split.attention_bsr_split_bf16, splits=None if splits == "auto" else splits)
         if fused_backward:                     # the backward kernels read the forward's out and its log-sum-exp
-            out, lse = ops.attention_bsr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, mask=mask, out_bf16=out_bf16, return_lse=True)
+            out, lse = attend(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, mask=mask, out_bf16=out_bf16, return_lse=True)
             ctx.save_for_backward(q, k, v, out, lse)
             return out.view(torch.bfloat16) if out_bf16 else out
-        out = ops.attention_bsr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, mask=mask, out_bf16=out_bf16)
+        out = attend(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, mask=mask, out_bf16=out_bf16)
         ctx.save_for_backward(q, k, v)
         return out.view(torch.bfloat16) if out_bf16 else out
 
@@ -566,14 +571,14 @@ class _FusedBlockSparseAttention(torch.autograd.Function):
     def backward(ctx, grad_out):
         a, needs = ctx.a, ctx.needs_input_grad
         if not any(needs[:3]):
-            return (None,) * 8
+            return (None,) * 9
         if ctx.fused_backward:
             q, k, v, out, lse = ctx.saved_tensors
             grad_out = grad_out.contiguous()       # e.g. out.sum().backward() hands in an expanded scalar
             g = ops.f32_to_bf16(grad_out) if grad_out.dtype == torch.float32 else _bits(grad_out)
             grads = ops.attention_bsr_bwd_bf16(a.fwd, a.tpattern, a.perm32(), _bits(q), _bits(k), _bits(v), out, lse, g, scale=ctx.scale,
                                                mask=ctx.mask, grads_bf16=True, need=tuple(needs[:3]))
-            return (*(None if x is None else x.view(torch.bfloat16) for x in grads), None, None, None, None, None)
+            return (*(None if x is None else x.view(torch.bfloat16) for x in grads), None, None, None, None, None, None)
         q, k, v = ctx.saved_tensors
         heads = [None] if q.dim() == 2 else range(q.shape[0])
         grads = ([], [], [])
@@ -585,10 +590,10 @@ class _FusedBlockSparseAttention(torch.autograd.Function):
             for held, grad in zip(grads, _attention_grads(a, qh, kh, vh, p, gh, ctx.scale, needs)):
                 held.append(grad)
         merged = [None if held[0] is None else (held[0] if q.dim() == 2 else torch.stack(held)) for held in grads]
-        return (*merged, None, None, None, None, None)
+        return (*merged, None, None, None, None, None, None)
 
 
-def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.float32, fused=False, fused_backward=False):
+def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.float32, fused=False, fused_backward=False, splits=None):
     """Attention on A's block pattern in bf16: matrix row r attends to the columns of the blocks A stores in r's block row.
 
         S = ops.sddmm_bsr_bf16(q, k)                               # fp32 [num_blocks, bS, bS]: <q_r, k_c>, fp32 accumulation
@@ -618,13 +623,23 @@ def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.fl
     ops.attention_bsr_bwd_bf16 call for all heads -- at most two launches, S, P, dP and dS never written -- asking only for the
     gradients autograd needs.  The gradients are bfloat16; they differ from the chain's by roundings (P is recomputed as
     exp(z - lse) in fp32 and dS uses delta = <grad_out, out> in place of <P, dP>) and are held to the derived tolerance of
-    include/mispmm_attn_bwd.h."""
+    include/mispmm_attn_bwd.h.
+    splits (only with fused=True; None by default, which changes nothing): an integer from 1 to 64, or "auto", takes the forward
+    through attn_bsr_split.attention_bsr_split_bf16 -- every block row dealt to that many waves and merged, two launches, for
+    few rows against very many keys; "auto" lets its rule choose (and run the one-wave kernel where it gives 1).  Both
+    backwards are unchanged: the recomputing one does not read out, the fused one reads the out and lse it is given."""
+    if splits is not None:
+        if not fused:
+            raise ValueError("splits deals the block rows of the fused forward to several waves: it needs fused=True")
+        if splits != "auto":
+            from . import attn_bsr_split
+            attn_bsr_split._check_splits(splits)
     ops._require_gpu(a.fwd.block_row_ptrs, q, k, v, mask)
     out_bf16 = _check_out_dtype(out_dtype)
     if fused_backward and not fused:
         raise ValueError("fused_backward=True is the backward of the fused forward: it needs fused=True")
     if fused:
-        return _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16, bool(fused_backward))
+        return _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16, bool(fused_backward), splits)
     for t, rows, what in ((q, a.fwd.num_rows, "q"), (k, a.fwd.num_cols, "k"), (v, a.fwd.num_cols, "v")):
         if t.dtype != torch.bfloat16:
             raise ValueError(f"{what} must be torch.bfloat16")
@@ -644,7 +659,7 @@ def block_sparse_attention(a, q, k, v, scale=None, mask=None, out_dtype=torch.fl
     return _BlockSparseAttention.apply(q, k, v, a, float(scale), mask, out_bf16)
 
 
-def _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16, fused_backward=False):
+def _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16, fused_backward=False, splits=None):
     dims = {t.dim() for t in (q, k, v)}
     if dims not in ({2}, {3}):
         raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
@@ -665,7 +680,7 @@ def _fused_block_sparse_attention(a, q, k, v, scale, mask, out_bf16, fused_backw
         mask = mask.detach().contiguous()
     if scale is None:
         scale = q.shape[-1] ** -0.5
-    return _FusedBlockSparseAttention.apply(q, k, v, a, float(scale), mask, out_bf16, fused_backward)
+    return _FusedBlockSparseAttention.apply(q, k, v, a, float(scale), mask, out_bf16, fused_backward, splits)
 
 
 # ---- the CSR product with B in bf16 (ops.spmm_csr_bf16): fp32 values, bf16 activations

@@ -1054,16 +1054,9 @@ def _attn_operand(t, rows, heads, what):
     return t, ld, (t.stride(0) if t.shape[0] > 1 else 0)
 
 
-def attention_bsr_bf16(a, q, k, v, scale=None, mask=None, out_bf16=False, return_lse=False, out=None, lse=None, stream=None):
-    """Fused block-sparse attention forward (mispmm_attn_bsr_bf16, libmispmm_attn.so): for every head, out = softmax over each
-    matrix row of (scale * q k^T + mask) on A's stored blocks, times v -- one launch for all heads, the scores and the weights
-    never written.  a: DeviceBSR [M x K] of 16 x 16 or 32 x 32 blocks (index arrays used); q: [M, D], k: [K, D], v: [K, Dv]
-    int16 tensors of bf16 bits, or [H, ...] with any head and row strides whose last dimension is contiguous (e.g. a permuted
-    [M, H, D]); D and Dv multiples of 8 up to 128.  scale defaults to D ** -0.5; mask: float32 [num_blocks, bS, bS], added to
-    the scaled scores, -Inf = masked, shared by the heads.  Returns out, [M, Dv] or [H, M, Dv], float32 or int16 bf16 bits
-    with out_bf16; with return_lse (out, lse), lse the float32 [M] or [H, M] log-sum-exp of each row.  out= and lse= take
-    the results where given: out of the result's shape with a contiguous last dimension, lse contiguous."""
-    from . import capi_attn
+def _attn_bsr_args(a, q, k, v, scale, mask, out_bf16, return_lse, out, lse, stream):
+    """(the arguments of mispmm_attn_bsr_bf16, result, lse, heads, Dv) of a fused forward on a BSR pattern: the operand contract of
+    attention_bsr_bf16, checked once for every front that takes it (attn_bsr_split.attention_bsr_split_bf16 appends its own)."""
     _require_gpu(a.block_row_ptrs, q, k, v, mask, out, lse)
     _square_blocks(a)
     bs = a.block_row_size
@@ -1099,11 +1092,24 @@ def attention_bsr_bf16(a, q, k, v, scale=None, mask=None, out_bf16=False, return
                             or not lse.is_contiguous()):
         raise ValueError(f"lse must be a contiguous float32 tensor of shape {(heads, a.num_rows) if batched else (a.num_rows,)}")
     o_head = out3.stride(0) if heads > 1 else 0
-    capi_attn.check(capi_attn.lib().mispmm_attn_bsr_bf16(
-        _stream_ptr(stream), heads, a.num_rows // bs, a.num_cols, bs, a.num_blocks, _p(a.block_row_ptrs), _p(a.block_col_idxs),
-        _p(q3), ldq, q_head, _p(k3), ldk, k_head, _p(v3), ldv, v_head, d, dv, _p(mask), float(scale), _p(out3), out3.stride(1), o_head,
-        int(bool(out_bf16)), _p(lse)))
-    result = out if out is not None else (out3 if batched else out3[0])
+    args = (_stream_ptr(stream), heads, a.num_rows // bs, a.num_cols, bs, a.num_blocks, _p(a.block_row_ptrs), _p(a.block_col_idxs),
+            _p(q3), ldq, q_head, _p(k3), ldk, k_head, _p(v3), ldv, v_head, d, dv, _p(mask), float(scale), _p(out3), out3.stride(1), o_head,
+            int(bool(out_bf16)), _p(lse))
+    return args, (out if out is not None else (out3 if batched else out3[0])), lse, heads, dv
+
+
+def attention_bsr_bf16(a, q, k, v, scale=None, mask=None, out_bf16=False, return_lse=False, out=None, lse=None, stream=None):
+    """Fused block-sparse attention forward (mispmm_attn_bsr_bf16, libmispmm_attn.so): for every head, out = softmax over each
+    matrix row of (scale * q k^T + mask) on A's stored blocks, times v -- one launch for all heads, the scores and the weights
+    never written.  a: DeviceBSR [M x K] of 16 x 16 or 32 x 32 blocks (index arrays used); q: [M, D], k: [K, D], v: [K, Dv]
+    int16 tensors of bf16 bits, or [H, ...] with any head and row strides whose last dimension is contiguous (e.g. a permuted
+    [M, H, D]); D and Dv multiples of 8 up to 128.  scale defaults to D ** -0.5; mask: float32 [num_blocks, bS, bS], added to
+    the scaled scores, -Inf = masked, shared by the heads.  Returns out, [M, Dv] or [H, M, Dv], float32 or int16 bf16 bits
+    with out_bf16; with return_lse (out, lse), lse the float32 [M] or [H, M] log-sum-exp of each row.  out= and lse= take
+    the results where given: out of the result's shape with a contiguous last dimension, lse contiguous."""
+    from . import capi_attn
+    args, result, lse, _, _ = _attn_bsr_args(a, q, k, v, scale, mask, out_bf16, return_lse, out, lse, stream)
+    capi_attn.check(capi_attn.lib().mispmm_attn_bsr_bf16(*args))
     return (result, lse) if return_lse else result
 
 
