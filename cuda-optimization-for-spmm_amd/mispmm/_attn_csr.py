@@ -134,7 +134,10 @@ def _written(kind, narrow, flag):
     return torch.float32, f"a float32 tensor ({flag}=False)", (0,)
 
 
-def forward(name, kind, a, q, k, v, scale, bias, out_bf16, return_lse, out, lse, stream):
+def _forward_args(name, kind, a, q, k, v, scale, bias, out_bf16, return_lse, out, lse, stream, also=()):
+    """The preparation of a forward call, for forward() and for the split-row front (attn_csr_split.py): every refusal in its
+    order, then the results not given allocated.  also: further tensors of the caller that must be on the device.  Returns (the
+    C arguments from the stream to lse, the result to hand back, lse, heads, dv)."""
     _f32_pattern(name, a)
     (q3, ldq, q_head), (k3, ldk, k_head), (v3, ldv, v_head), batched = _qkv(kind, a, q, k, v)
     heads, d, dv = q3.shape[0], q3.shape[2], v3.shape[2]
@@ -157,7 +160,7 @@ def forward(name, kind, a, q, k, v, scale, bias, out_bf16, return_lse, out, lse,
     if lse is not None:
         _per_row(lse, lse_shape, "lse")
     # every defect of an operand is named above, on tensors of any device; only then: there is no CPU path
-    ops._require_gpu(a.row_ptrs, q, k, v, bias, out, lse)
+    ops._require_gpu(a.row_ptrs, q, k, v, bias, out, lse, *also)
     if out3 is None:
         out3 = torch.empty(shape, dtype=o_dtype, device=q.device)
     if lse is None and return_lse:
@@ -165,9 +168,14 @@ def forward(name, kind, a, q, k, v, scale, bias, out_bf16, return_lse, out, lse,
     ldo = out3.stride(1) if shape[1] > 1 else max(dv, out3.stride(1))
     o_head = out3.stride(0) if heads > 1 else 0
     _p = ops._p
-    _call(kind.fwd, ops._stream_ptr(stream), heads, a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs), _p(q3), q_head, ldq,
-          _p(k3), k_head, ldk, d, _p(v3), v_head, ldv, dv, float(scale), _p(bias), bias_head, _p(out3), o_head, ldo, *narrow, _p(lse))
-    result = out if out is not None else (out3 if batched else out3[0])
+    args = (ops._stream_ptr(stream), heads, a.num_rows, a.num_cols, a.nnz, _p(a.row_ptrs), _p(a.col_idxs), _p(q3), q_head, ldq,
+            _p(k3), k_head, ldk, d, _p(v3), v_head, ldv, dv, float(scale), _p(bias), bias_head, _p(out3), o_head, ldo, *narrow, _p(lse))
+    return args, (out if out is not None else (out3 if batched else out3[0])), lse, heads, dv
+
+
+def forward(name, kind, a, q, k, v, scale, bias, out_bf16, return_lse, out, lse, stream):
+    args, result, lse, _, _ = _forward_args(name, kind, a, q, k, v, scale, bias, out_bf16, return_lse, out, lse, stream)
+    _call(kind.fwd, *args)
     return (result, lse) if return_lse else result
 
 

@@ -243,6 +243,22 @@ def _lse_backward(ctx, bwd, dbias, q, k, v, out, lse, grad_out, **kw):
     return grads, grad_bias
 
 
+def _check_csr_splits(splits):
+    """splits of the fused forward on a CSR pattern: None, "auto" or an integer attn_csr_split takes."""
+    if splits is not None and splits != "auto":
+        from . import attn_csr_split
+        attn_csr_split._check_splits(splits)
+
+
+def _csr_attend(one_launch, split, splits):
+    """The forward of a fused CSR attention Function: `one_launch`, or with splits the split-row front of attn_csr_split.py
+    (two launches, long rows dealt to several lane groups; "auto": its default rule)."""
+    if splits is None:
+        return one_launch
+    from . import attn_csr_split
+    return functools.partial(getattr(attn_csr_split, split), splits=None if splits == "auto" else splits)
+
+
 class _FusedSparseAttention(torch.autograd.Function):
     """The forward in one launch for all heads (ops.attention_csr).  q, k, v are saved and the weights are not: the backward
     recomputes the scores and P head by head with the FAST kernels of the four-launch forward and runs its gradient chain, so
@@ -250,19 +266,19 @@ class _FusedSparseAttention(torch.autograd.Function):
     the head's bias gradient: returned where the bias requires one (sparse_attention hands in a bias that does only with
     bias_grad=True)."""
     @staticmethod
-    def forward(ctx, q, k, v, a, scale, bias):
+    def forward(ctx, q, k, v, a, scale, bias, splits=None):
         q, k, v = q.detach(), k.detach(), v.detach()
         bias = None if bias is None else bias.detach()
         ctx.a, ctx.scale, ctx.bias = a, scale, bias
         ctx.save_for_backward(q, k, v)
-        return ops.attention_csr(a.fwd, q, k, v, scale=scale, bias=bias)
+        return _csr_attend(ops.attention_csr, "attention_csr_split", splits)(a.fwd, q, k, v, scale=scale, bias=bias)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
         a, needs, scale, bias = ctx.a, ctx.needs_input_grad, ctx.scale, ctx.bias
         if not any(needs[:3]) and not needs[5]:
-            return (None,) * 6
+            return (None,) * 7
         q, k, v = ctx.saved_tensors
         heads = [None] if q.dim() == 2 else range(q.shape[0])
         grads = ([], [], [])
@@ -289,7 +305,7 @@ class _FusedSparseAttention(torch.autograd.Function):
                 held.append(grad)
         merged = [None if held[0] is None else (held[0] if q.dim() == 2 else torch.stack(held)) for held in grads]
         grad_bias = _bias_grad(grads_b[0] if q.dim() == 2 else torch.stack(grads_b), bias) if needs[5] else None
-        return (*merged, None, None, grad_bias)
+        return (*merged, None, None, grad_bias, None)
 
 
 class _FusedSparseAttentionFusedBwd(torch.autograd.Function):
@@ -298,10 +314,10 @@ class _FusedSparseAttentionFusedBwd(torch.autograd.Function):
     bias that requires a gradient gets it by one launch more (attn_csr_dbias.attention_csr_dbias), made only then; the backward
     call is skipped where q, k and v need nothing."""
     @staticmethod
-    def forward(ctx, q, k, v, a, scale, bias):
+    def forward(ctx, q, k, v, a, scale, bias, splits=None):
         q, k, v = q.detach(), k.detach(), v.detach()
         bias = None if bias is None else bias.detach()
-        out, lse = ops.attention_csr(a.fwd, q, k, v, scale=scale, bias=bias, return_lse=True)
+        out, lse = _csr_attend(ops.attention_csr, "attention_csr_split", splits)(a.fwd, q, k, v, scale=scale, bias=bias, return_lse=True)
         ctx.a, ctx.scale, ctx.bias = a, scale, bias
         ctx.save_for_backward(q, k, v, out, lse)
         return out
@@ -312,12 +328,12 @@ class _FusedSparseAttentionFusedBwd(torch.autograd.Function):
         from . import attn_csr_dbias
         needs = ctx.needs_input_grad
         if not any(needs[:3]) and not needs[5]:
-            return (None,) * 6
+            return (None,) * 7
         grads, grad_bias = _lse_backward(ctx, ops.attention_csr_bwd, attn_csr_dbias.attention_csr_dbias, *ctx.saved_tensors, _dense_grad(grad_out))
-        return (*grads, None, None, grad_bias)
+        return (*grads, None, None, grad_bias, None)
 
 
-def _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward=False):
+def _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward=False, splits=None):
     dtype = a.fwd.data.dtype
     if dtype != torch.float32:
         raise ValueError("fused=True takes a float32 matrix: the fused kernel has one arithmetic, fp32")
@@ -331,11 +347,11 @@ def _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward=False):
     if scale is None:
         scale = q.shape[-1] ** -0.5
     if fused_backward:
-        return _FusedSparseAttentionFusedBwd.apply(q, k, v, a, float(scale), bias)
-    return _FusedSparseAttention.apply(q, k, v, a, float(scale), bias)
+        return _FusedSparseAttentionFusedBwd.apply(q, k, v, a, float(scale), bias, splits)
+    return _FusedSparseAttention.apply(q, k, v, a, float(scale), bias, splits)
 
 
-def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=False, fused_backward=False, bias_grad=False):
+def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=False, fused_backward=False, bias_grad=False, splits=None):
     """Attention on A's pattern: row r attends to the columns A stores in row r.
 
         scores = sddmm(a, q * scale, k)        # [nnz]   <q_r, k_c> for every stored (r, c)
@@ -364,13 +380,21 @@ def sparse_attention(a, q, k, v, scale=None, acc="reference", bias=None, fused=F
     ds of each head (ops.softmax_csr_bwd) IS that head's bias gradient and is returned.  fused_backward=True: one launch more
     for all heads (attn_csr_dbias.attention_csr_dbias, include/mispmm_attn_csr_dbias.h), made only where the bias needs a
     gradient; ops.attention_csr_bwd is skipped where nothing else does.  A bias [nnz] shared by H heads gets the heads' sum (one
-    torch.sum over the per-head result)."""
+    torch.sum over the per-head result).
+    splits (only with fused=True; None by default, which changes nothing): an integer from 1 to 256, or "auto", takes the forward
+    through attn_csr_split.attention_csr_split -- two launches, every long row dealt to up to `splits` lane groups, for few rows
+    against very many keys; "auto" is its default rule, which may choose the one-launch kernel.  out and lse differ from the
+    one-launch result by roundings inside the same tolerances (splits=1: not at all).  The backwards are unchanged: the
+    recomputing one does not read out, the fused one reads the out and lse it is given."""
+    if splits is not None and not fused:
+        raise ValueError("splits deals the long rows of the fused forward to several lane groups: it needs fused=True")
+    _check_csr_splits(splits)
     if fused_backward and not fused:
         raise ValueError("fused_backward=True needs fused=True: the fused backward reads the fused forward's out and lse")
     ops._require_gpu(a.fwd.row_ptrs, q, k, v, bias)
     bias = _bias_gate(bias, bias_grad, a.fwd.data.dtype, ", like the matrix")
     if fused:
-        return _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward)
+        return _fused_sparse_attention(a, q, k, v, scale, bias, fused_backward, splits)
     dtype = a.fwd.data.dtype
     _check_operand(q, a.fwd.num_rows, dtype, "q")
     _check_operand(k, a.fwd.num_cols, dtype, "k")
@@ -743,13 +767,14 @@ def spmm_bf16(a, values, b, out_dtype=torch.bfloat16, acc="fast", sddmm="f32"):
 
 
 # ---- fused attention on a CSR pattern with the activations in bf16 (attn_csr_bf16.attention_csr_bf16)
-def _bf16_forward(ctx, q, k, v, a, scale, bias):
+def _bf16_forward(ctx, q, k, v, a, scale, bias, splits=None):
     """The forward of both Functions below: one launch for all heads, reading bf16; q, k, v, the fp32 out and lse are saved and
     the fp32 out returned."""
     from . import attn_csr_bf16
     q, k, v = q.detach(), k.detach(), v.detach()
     bias = None if bias is None else bias.detach()
-    out, lse = attn_csr_bf16.attention_csr_bf16(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, bias=bias, return_lse=True)
+    attend = _csr_attend(attn_csr_bf16.attention_csr_bf16, "attention_csr_split_bf16", splits)
+    out, lse = attend(a.fwd, _bits(q), _bits(k), _bits(v), scale=scale, bias=bias, return_lse=True)
     ctx.a, ctx.scale, ctx.bias = a, scale, bias
     ctx.save_for_backward(q, k, v, out, lse)
     return out
@@ -760,8 +785,8 @@ class _SparseAttentionBf16(torch.autograd.Function):
     is ops.attention_csr_bwd on the widened q, k, v with the saved fp32 out and lse, every gradient rounded once.  A bias that
     requires a gradient gets it in fp32 by attn_csr_dbias.attention_csr_dbias on the same widened operands."""
     @staticmethod
-    def forward(ctx, q, k, v, a, scale, bias, out_bf16):
-        out = _bf16_forward(ctx, q, k, v, a, scale, bias)
+    def forward(ctx, q, k, v, a, scale, bias, out_bf16, splits=None):
+        out = _bf16_forward(ctx, q, k, v, a, scale, bias, splits)
         return ops.f32_to_bf16(out).view(torch.bfloat16) if out_bf16 else out
 
     @staticmethod
@@ -770,7 +795,7 @@ class _SparseAttentionBf16(torch.autograd.Function):
         from . import attn_csr_dbias
         needs = ctx.needs_input_grad
         if not any(needs[:3]) and not needs[5]:
-            return (None,) * 7
+            return (None,) * 8
         q, k, v, out, lse = ctx.saved_tensors
         if grad_out.dtype == torch.bfloat16:
             grad_out = ops.bf16_to_f32(_bits(grad_out))            # exact; a view that is not contiguous is copied there
@@ -778,7 +803,7 @@ class _SparseAttentionBf16(torch.autograd.Function):
             grad_out = _dense_grad(grad_out)
         qf, kf, vf = (ops.bf16_to_f32(_bits(t)) for t in (q, k, v))
         grads, grad_bias = _lse_backward(ctx, ops.attention_csr_bwd, attn_csr_dbias.attention_csr_dbias, qf, kf, vf, out, lse, grad_out)
-        return (*(None if g is None else ops.f32_to_bf16(g).view(torch.bfloat16) for g in grads), None, None, grad_bias, None)
+        return (*(None if g is None else ops.f32_to_bf16(g).view(torch.bfloat16) for g in grads), None, None, grad_bias, None, None)
 
 
 class _SparseAttentionBf16FusedBwd(torch.autograd.Function):
@@ -787,8 +812,8 @@ class _SparseAttentionBf16FusedBwd(torch.autograd.Function):
     memory, `need` set from the inputs that require a gradient.  A bias that requires a gradient gets it in fp32 by one launch
     more that reads bf16 itself (attn_csr_dbias.attention_csr_dbias_bf16)."""
     @staticmethod
-    def forward(ctx, q, k, v, a, scale, bias):
-        return ops.f32_to_bf16(_bf16_forward(ctx, q, k, v, a, scale, bias)).view(torch.bfloat16)
+    def forward(ctx, q, k, v, a, scale, bias, splits=None):
+        return ops.f32_to_bf16(_bf16_forward(ctx, q, k, v, a, scale, bias, splits)).view(torch.bfloat16)
 
     @staticmethod
     @once_differentiable
@@ -796,14 +821,14 @@ class _SparseAttentionBf16FusedBwd(torch.autograd.Function):
         from . import attn_csr_bf16, attn_csr_dbias
         needs = ctx.needs_input_grad
         if not any(needs[:3]) and not needs[5]:
-            return (None,) * 6
+            return (None,) * 7
         q, k, v, out, lse = ctx.saved_tensors
         grads, grad_bias = _lse_backward(ctx, attn_csr_bf16.attention_csr_bf16_bwd, attn_csr_dbias.attention_csr_dbias_bf16, _bits(q), _bits(k),
                                          _bits(v), out, lse, _bits(_dense_grad(grad_out)), grads_bf16=True)
-        return (*(None if g is None else g.view(torch.bfloat16) for g in grads), None, None, grad_bias)
+        return (*(None if g is None else g.view(torch.bfloat16) for g in grads), None, None, grad_bias, None)
 
 
-def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfloat16, fused_backward=False, bias_grad=False):
+def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfloat16, fused_backward=False, bias_grad=False, splits=None):
     """Attention on A's pattern with the activations in bfloat16: row r attends to the columns A stores in row r, one launch
     for all heads (attn_csr_bf16.attention_csr_bf16: fp32 arithmetic on the exactly widened operands, online softmax, neither
     scores nor weights written, no fp32 copy of q, k or v).
@@ -827,7 +852,10 @@ def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfl
     for all heads, made only then: attn_csr_dbias.attention_csr_dbias on the widened operands the default backward holds, or
     with fused_backward=True attn_csr_dbias.attention_csr_dbias_bf16, which reads bf16 itself.  The backward call proper is
     skipped where q, k and v need nothing; their gradients are the same bits as with a constant bias.  A bias [nnz] shared by
-    H heads gets the heads' sum (one torch.sum over the per-head result)."""
+    H heads gets the heads' sum (one torch.sum over the per-head result).
+    splits (None by default, which changes nothing): an integer from 1 to 256, or "auto", takes the forward through
+    attn_csr_split.attention_csr_split_bf16, as sparse_attention's splits does; the backwards are unchanged."""
+    _check_csr_splits(splits)
     if fused_backward and out_dtype == torch.float32:
         raise ValueError("fused_backward=True needs out_dtype=torch.bfloat16: with a float32 out, grad_out would be float32, and the fused "
                          "bf16 backward reads a bfloat16 grad_out")
@@ -840,5 +868,5 @@ def sparse_attention_bf16(a, q, k, v, scale=None, bias=None, out_dtype=torch.bfl
     if scale is None:
         scale = q.shape[-1] ** -0.5
     if fused_backward:
-        return _SparseAttentionBf16FusedBwd.apply(q, k, v, a, float(scale), bias)
-    return _SparseAttentionBf16.apply(q, k, v, a, float(scale), bias, out_bf16)
+        return _SparseAttentionBf16FusedBwd.apply(q, k, v, a, float(scale), bias, splits)
+    return _SparseAttentionBf16.apply(q, k, v, a, float(scale), bias, out_bf16, splits)
