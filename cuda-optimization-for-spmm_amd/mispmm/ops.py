@@ -82,7 +82,8 @@ def check_host(m):
 # here, once, before any call into a library.  The checks read attributes only: no synchronisation, no allocation, no copy.
 _DENSE_WORDS = {torch.float32: "{what}: dense operands must be 2-D float32 with unit column stride",
                 torch.float64: "{what}: with a float64 A, dense operands must be 2-D float64 with unit column stride",
-                torch.int16: "{what} must be a 2-D int16 tensor of bf16 bits with unit column stride"}
+                torch.int16: "{what} must be a 2-D int16 tensor of bf16 bits with unit column stride",
+                torch.uint8: "{what} must be a 2-D tensor of fp8 e4m3 bytes with unit column stride"}
 
 
 def _acc_mode(acc):
