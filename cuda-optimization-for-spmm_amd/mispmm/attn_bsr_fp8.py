@@ -41,28 +41,23 @@ def _head_scale(s, what, heads, device):
     return s
 
 
-def attention_bsr_fp8(a, q, k, v, q_scale=None, k_scale=None, v_scale=None, scale=None, mask=None, out_bf16=False, return_lse=False,
-                      out=None, lse=None, stream=None):
-    """Fused block-sparse attention forward on e4m3 operands (mispmm_attn_bsr_fp8): for every head, out = v_scale * softmax over
-    each matrix row of (scale * q_scale * k_scale * q k^T + mask) on A's stored blocks, times v -- one launch for all heads.
-    a: DeviceBSR [M x K] of 16 x 16 or 32 x 32 blocks (index arrays used); q: [M, D], k: [K, D], v: [K, Dv]
-    torch.float8_e4m3fn tensors or their uint8 bytes, or [H, ...] with any head and row strides whose last dimension is
-    contiguous (e.g. a permuted [M, H, D]) and that meet the header's alignment; D a multiple of 16 and Dv of 8, up to 128.
-    q_scale, k_scale, v_scale: one scale per head, a float32 device tensor of H elements (what quantize_heads returned) or a
-    Python float, finite and > 0; None is no multiply.  scale defaults to D ** -0.5; mask: float32 [num_blocks, bS, bS], -Inf =
-    masked.  Returns out, [M, Dv] or [H, M, Dv], float32 or int16 bf16 bits with out_bf16; with return_lse (out, lse).  out=
-    and lse= take the results where given: out of the result's shape with a contiguous last dimension, lse contiguous."""
-    from . import capi_attn_fp8
+def _fp8_args(a, q, k, v, q_scale, k_scale, v_scale, scale, mask, out_bf16, return_lse, out, lse, stream, shared_kv=False):
+    """The checks and the operand preparation of both fp8 fronts: (call, result, lse, H, Hkv, Dv), call(entry, *more) making the
+    C call.  shared_kv: k and v may hold Hkv heads with H % Hkv == 0 (2-D beside a 3-D q: Hkv = 1), and k_scale and
+    v_scale Hkv elements; otherwise Hkv == H."""
     _require_gpu(a.block_row_ptrs, q, k, v, mask, out, lse)
     _square_blocks(a)
     bs = a.block_row_size
-    if q.dim() != k.dim() or q.dim() != v.dim():
+    if (q.dim() != k.dim() and not (shared_kv and q.dim() == 3 and k.dim() == 2)) or k.dim() != v.dim():
         raise ValueError(f"q, k and v must all be 2-D or all [H, ...], not {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
     batched = q.dim() == 3
     q3, ldq, q_head = _operand(q, a.num_rows, None, "q")
     heads = q3.shape[0]
-    k3, ldk, k_head = _operand(k, a.num_cols, heads, "k")
-    v3, ldv, v_head = _operand(v, a.num_cols, heads, "v")
+    k3, ldk, k_head = _operand(k, a.num_cols, None if shared_kv else heads, "k")
+    kv_heads = k3.shape[0]
+    if kv_heads == 0 or heads % kv_heads != 0:
+        raise ValueError(f"the {heads} heads of q must be a multiple of the {kv_heads} heads of k and v")
+    v3, ldv, v_head = _operand(v, a.num_cols, kv_heads, "v")
     d, dv = q3.shape[2], v3.shape[2]
     if k3.shape[2] != d:
         raise ValueError(f"q and k must have the same number of columns, not {d} and {k3.shape[2]}")
@@ -71,7 +66,8 @@ def attention_bsr_fp8(a, q, k, v, q_scale=None, k_scale=None, v_scale=None, scal
             raise ValueError(f"the fp8 fused attention kernel takes {what} in multiples of {step} up to {MAX_WIDTH}, not {width}")
     if mask is not None:
         _block_array(a, mask, (torch.float32,), "mask")
-    scales = [_head_scale(s, what, heads, q.device) for s, what in ((q_scale, "q_scale"), (k_scale, "k_scale"), (v_scale, "v_scale"))]
+    scales = [_head_scale(s, what, n, q.device) for s, what, n in ((q_scale, "q_scale", heads), (k_scale, "k_scale", kv_heads),
+                                                                   (v_scale, "v_scale", kv_heads))]
     if scale is None:
         scale = d ** -0.5
     dtype = torch.int16 if out_bf16 else torch.float32
@@ -87,11 +83,28 @@ def attention_bsr_fp8(a, q, k, v, q_scale=None, k_scale=None, v_scale=None, scal
         lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
     if lse is not None and (lse.dtype != torch.float32 or tuple(lse.shape) != lse_shape or not lse.is_contiguous()):
         raise ValueError(f"lse must be a contiguous float32 tensor of shape {lse_shape}")
-    capi_attn_fp8.check(capi_attn_fp8.lib().mispmm_attn_bsr_fp8(
-        _stream_ptr(stream), heads, a.num_rows // bs, a.num_cols, bs, a.num_blocks, _p(a.block_row_ptrs), _p(a.block_col_idxs), _p(q3), ldq,
-        q_head, _p(k3), ldk, k_head, _p(v3), ldv, v_head, d, dv, _p(mask), float(scale), _p(scales[0]), _p(scales[1]), _p(scales[2]), _p(out3),
-        out3.stride(1), out3.stride(0) if heads > 1 else 0, int(bool(out_bf16)), _p(lse)))
-    result = out if out is not None else (out3 if batched else out3[0])
+    def call(entry, *more):
+        """entry(the arguments of mispmm_attn_bsr_fp8 in its order, *more); the scales made of a float live until it returns."""
+        return entry(_stream_ptr(stream), heads, a.num_rows // bs, a.num_cols, bs, a.num_blocks, _p(a.block_row_ptrs), _p(a.block_col_idxs),
+                     _p(q3), ldq, q_head, _p(k3), ldk, k_head, _p(v3), ldv, v_head, d, dv, _p(mask), float(scale), _p(scales[0]), _p(scales[1]),
+                     _p(scales[2]), _p(out3), out3.stride(1), out3.stride(0) if heads > 1 else 0, int(bool(out_bf16)), _p(lse), *more)
+    return call, (out if out is not None else (out3 if batched else out3[0])), lse, heads, kv_heads, dv
+
+
+def attention_bsr_fp8(a, q, k, v, q_scale=None, k_scale=None, v_scale=None, scale=None, mask=None, out_bf16=False, return_lse=False,
+                      out=None, lse=None, stream=None):
+    """Fused block-sparse attention forward on e4m3 operands (mispmm_attn_bsr_fp8): for every head, out = v_scale * softmax over
+    each matrix row of (scale * q_scale * k_scale * q k^T + mask) on A's stored blocks, times v -- one launch for all heads.
+    a: DeviceBSR [M x K] of 16 x 16 or 32 x 32 blocks (index arrays used); q: [M, D], k: [K, D], v: [K, Dv]
+    torch.float8_e4m3fn tensors or their uint8 bytes, or [H, ...] with any head and row strides whose last dimension is
+    contiguous (e.g. a permuted [M, H, D]) and that meet the header's alignment; D a multiple of 16 and Dv of 8, up to 128.
+    q_scale, k_scale, v_scale: one scale per head, a float32 device tensor of H elements (what quantize_heads returned) or a
+    Python float, finite and > 0; None is no multiply.  scale defaults to D ** -0.5; mask: float32 [num_blocks, bS, bS], -Inf =
+    masked.  Returns out, [M, Dv] or [H, M, Dv], float32 or int16 bf16 bits with out_bf16; with return_lse (out, lse).  out=
+    and lse= take the results where given: out of the result's shape with a contiguous last dimension, lse contiguous."""
+    from . import capi_attn_fp8
+    call, result, lse, _, _, _ = _fp8_args(a, q, k, v, q_scale, k_scale, v_scale, scale, mask, out_bf16, return_lse, out, lse, stream)
+    capi_attn_fp8.check(call(capi_attn_fp8.lib().mispmm_attn_bsr_fp8))
     return (result, lse) if return_lse else result
 
 
